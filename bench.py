@@ -16,7 +16,11 @@ datasets exist offline).  ``--config 4`` (8 views x 32 frames x 64x64 latent) an
 Inputs are resident in HBM before the timed region.  For N > 1 the SAME job is sharded over the GPUs (CFG halves x views x
 frames, animate3d_amd/parallel.py) => strong scaling; value = steps/s of the whole job.
 
-Rank 0 prints ONE JSON line.  It carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes the last step's output if
+``--dump-outputs DIR`` is given (DIR/sample.npy, float32; past 64 MB a fixed seeded sample of its elements) and prints the line
+with the headline figures (metric, value, unit, higher_is_better, dtype, ms_per_step) and the work per step derived from them;
+for N > 1 the line's ``communication`` object holds the layout and the bytes / collectives each rank received.
+``--full`` adds everything else, measured after (or, for the roofline, during) the timed steps:
   roofline     — the dominant kernel as rocprofv3 names it (flash_attn_dm_kernel<5, 2> in both storage types:
                  level-0 multi-view / first-frame attention, head_dim 40): algorithmic FLOPs per launch / mean launch duration measured with HIP events on the
                  launch stream inside the timed region, against the dense bf16 MFMA peak; ``ceilings`` adds the second
@@ -30,7 +34,10 @@ Rank 0 prints ONE JSON line.  It carries
                  (fewer only past a 150-s budget), thread count chosen by a 2-second matmul probe over the CPUs this process may use.
   box          — calibration kernels outside the timed region (8192^3 GEMM, the level-0 attention launch on zero-filled and on random
                  inputs, a 336 MB LayerNorm, the shader clock if rocm-smi answers): compute-bound kernels run at a power-limited clock
-                 that differs by several per cent between boxes, so round-over-round deltas are quoted against these.
+                 that differs by several per cent between boxes, so round-over-round deltas are quoted against these;
+  communication.ms_per_step_without_collectives / exposed_communication_ms_per_step — N > 1: the steps re-timed with the data-path
+                 collectives replaced by local copies.
+``--no-groups``, ``--no-box`` and ``--no-cpu-baseline`` drop single parts of ``--full``.
 ``--dtype`` selects the storage type of the kernels; the default is the dtype BASELINE.json states for the configuration (2: bf16, 4 and
 5: fp16) and the line's ``dtype`` reports what ran.  ``--graph`` adds the same steps replayed from a HIP graph (capture_graph).
 """
@@ -346,6 +353,22 @@ def _link_ms(plan, steps):
     return by / (peers * XGMI_LINK_GBS * 1e9) * 1e3
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, y):
+    """--dump-outputs: the UNet output of the last timed step as path/sample.npy in float32, so that two builds can be compared output
+    for output.  Past DUMP_BYTES (custom sizes; config 4 is 34 MB) a fixed seeded sample of its elements is written instead: the same
+    positions on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    y = y.detach().float()
+    if y.numel() * 4 > DUMP_BYTES:
+        idx = torch.randint(y.numel(), (DUMP_BYTES // 8,), generator=torch.Generator().manual_seed(0)).sort().values
+        y = y.flatten()[idx.to(y.device)]
+    np.save(os.path.join(path, "sample.npy"), y.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -356,11 +379,14 @@ def main():
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--latent", type=int, default=0)
     ap.add_argument("--layout", type=str, default="", help="multi-GPU: cfg,views,frames shard counts (default: CFG halves, then views, then frames)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline (HIP events around the "
+                    "dominant kernel inside the timed steps), groups, box, cpu_baseline and, for N > 1, the steps without collectives")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's output as DIR/sample.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-groups", action="store_true", help="skip the instrumented forward behind the 'groups' object")
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default=None, help="kernel storage type (default: what BASELINE.json states for the configuration)")
     ap.add_argument("--graph", action="store_true", help="also time the same steps replayed from a HIP graph (capture_graph)")
-    ap.add_argument("--shapes", action="store_true", help="print the instrumented forward per op shape on stderr (top 90 by time)")
+    ap.add_argument("--shapes", action="store_true", help="with --full: print the instrumented forward per op shape on stderr (top 90 by time)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU baseline (default: picked by a short GEMM probe)")
     ap.add_argument("--per-layer-conditioning", action="store_true", help="A/B: project the time embedding / text / IP tokens once per layer (54 small GEMMs, "
                     "rounds 1-5) instead of stacked (3 GEMMs, MVUNetMotionModel.stack_conditioning)")
@@ -371,6 +397,8 @@ def main():
                     "cfg,views,frames (its local rows, K|V projections over the gathered token count, q_len != kv_len attention, split-K off, CU "
                     "reservation while a gather would be in flight), every collective replaced by a local copy of the right size; the line's metric says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher — one rank per GPU under torch.distributed.run on a free local port; the
@@ -458,12 +486,14 @@ def main():
     for p_ in (par, rpar):
         if p_ is not None:
             p_.gather_bytes = p_.collectives = 0
-    ops.enabled = True
+    ops.enabled = args.full
     dt, y = timed_steps(args.steps)
     ops.enabled = False
     assert torch.isfinite(y).all()
     ms_per_step = dt / args.steps * 1e3
     value = args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
 
     # dominant kernel, measured live with HIP events on the launch stream
     durs = [a.elapsed_time(b) * 1e-3 for a, b in ops.events]
@@ -494,9 +524,10 @@ def main():
                     "flop_per_launch": flops, "share_of_step_time": sum(durs) / dt}
 
     comm = None
-    if par is not None:      # exposed communication = step time with the data-path collectives replaced by local copies
+    if par is not None:
         comm = {"layout": {"cfg": par.cfg_shards, "views": par.view_shards, "frames": par.frame_shards},
                 "received_bytes_per_rank_per_step": par.gather_bytes / args.steps, "collectives_per_step": par.collectives / args.steps}
+    if par is not None and args.full:      # exposed communication = step time with the data-path collectives replaced by local copies
         import torch.distributed as dist_
         real = (dist_.all_gather_into_tensor, dist_.broadcast, dist_.all_reduce)
 
@@ -532,7 +563,7 @@ def main():
         graph_ms = (time.perf_counter() - t0) / args.steps * 1e3
 
     groups = None
-    if not args.no_groups:
+    if args.full and not args.no_groups:
         ops.profile = True
         model(**inp)
         torch.cuda.synchronize()
@@ -555,8 +586,9 @@ def main():
                        f"cfg{par.cfg_shards} x views{par.view_shards} x frames{par.frame_shards} (token / K|V all-gathers over RCCL)"},
             "flop_per_step": work, "whole_step_tflops": work * value / 1e12,
             "whole_step_mfma_frac": work * value / 1e12 / (PEAK_BF16_TFLOPS * world),
-            "roofline": roofline,
         }
+        if args.full:
+            line["roofline"] = roofline
         if rpar is not None:
             # NOT the BASELINE metric: one rank's compute time of an N-GPU layout measured on one GPU (link time excluded)
             P = rpar.world
@@ -582,9 +614,9 @@ def main():
             line["groups"] = groups
         if comm is not None:
             line["communication"] = comm
-        if world == 1 and not args.no_box:
+        if args.full and world == 1 and not args.no_box:
             line["box"] = box_calibration(ops._ops, dev)
-        if world == 1 and not args.no_cpu_baseline and rpar is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and rpar is None:
             line["cpu_baseline"] = cpu_baseline(args.cpu_threads)
         print(json.dumps(line), flush=True)
     if world > 1:
