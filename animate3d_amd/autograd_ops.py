@@ -8,6 +8,7 @@ The reference trains the motion modules and the ``*_i2v`` projections with plain
 
     gemm            dX = dY W            (a3d_gemm on W^T),  dW = dY^T X (a3d_wgrad: split over the token axis),  db = a3d_colsum
     conv3x3         dX = conv(dY, flipped W^T) (+ a3d_zero_insert2x for stride 2, a3d_upsample2x_bwd behind the up-sampler)
+                    (dY and the weight zero-padded to 64 channels below 64 output channels: the VAE encoder's conv_out)
     gemm_geglu      projection recomputed, a3d_geglu_bwd, then as gemm
     flash_attn      a3d_flash_attn_bwd     temporal_attn  a3d_temporal_attn_bwd
     group_norm      a3d_group_norm_sums + a3d_group_norm_bwd        layer_norm  a3d_layer_norm_bwd
@@ -387,15 +388,21 @@ class _Conv3x3(torch.autograd.Function):
                 img = dy.reshape(B, 1, H, W, dy.shape[1]).permute(0, 4, 1, 2, 3).contiguous()
                 dx = base.gemm(base.im2col_in(img), aops.dgrad_weight_small(w, ctx.cin))
             else:
-                wd = aops.dgrad_weight(w, ctx.cin)
+                dyi = dy
+                if dy.shape[1] < 64:          # 8 ... 56 output channels (the VAE encoder's conv_out): the dgrad conv reads dY as its input, whose
+                    dyi = dy.new_zeros(dy.shape[0], 64)    # channels the kernel needs in multiples of 64 — dY and the dgrad weight zero-padded
+                    dyi[:, : dy.shape[1]] = dy
+                    wd = aops.dgrad_weight_pad64(w, ctx.cin)
+                else:
+                    wd = aops.dgrad_weight(w, ctx.cin)
                 if up2x:
                     He, We = (2 * H, 2 * W) if up_size is None else (int(up_size[0]), int(up_size[1]))
-                    du, _, _ = base.conv3x3(dy, B, He, We, wd, None)
+                    du, _, _ = base.conv3x3(dyi, B, He, We, wd, None)
                     dx = base.upsample2x_bwd(du, B, H, W, He, We)
                 elif stride == 2:
-                    dx, _, _ = base.conv3x3(base.zero_insert2x(dy, B, H, W), B, H, W, wd, None)
+                    dx, _, _ = base.conv3x3(base.zero_insert2x(dyi, B, H, W), B, H, W, wd, None)
                 else:
-                    dx, _, _ = base.conv3x3(dy, B, H, W, wd, None)
+                    dx, _, _ = base.conv3x3(dyi, B, H, W, wd, None)
         dres = dy if need[4] else None
         return None, dx, None, None, dres, None, None, None, None, None, None, None, None
 
@@ -597,6 +604,16 @@ class AutogradOps:
             out[:, : 9 * cout] = wd
             return out
         return self._cached(w, "ds", make)
+
+    def dgrad_weight_pad64(self, w, cin: int):
+        """Same for a conv with 8 ... 56 output channels: [Cin, (2-ky, 2-kx, co)] with co zero-padded to 64 (dY padded alike)."""
+        def make():
+            cout = w.shape[0]
+            wd = w.detach().reshape(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0)
+            out = torch.zeros((cin, 3, 3, 64), dtype=w.dtype, device=w.device)
+            out[..., :cout] = wd
+            return out.reshape(cin, 9 * 64)
+        return self._cached(w, "d64", make)
 
     def prefetch_scalars(self, tensors):
         """The kernels take merge weights by value (``a3d_gemm``'s ``alpha``): a trainable weight (AlphaBlender ``mix_factor``) has to be read

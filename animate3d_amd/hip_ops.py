@@ -89,6 +89,8 @@ _SIGNATURES = {
     "a3d_unpack_out": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int]),
     "a3d_gemm_f32out_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32]),
     "a3d_softmax_rows_f32_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
+    "a3d_softmax_rows_bwd_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32]),
+    "a3d_im2col_in_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f32]),
     "a3d_channel_mix_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_f32]),
     "a3d_cfg_ddim_step_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_f32, c_f32, c_f32]),
     # training path (include/animate3d_hip.h, "Training path" section)
@@ -114,10 +116,11 @@ _SIGNATURES = {
     "a3d_adamw_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp]),
 }
 # fp16-storage twins (include/animate3d_hip.h, last section): same signatures
+_UNSUFFIXED_TWINS = ("a3d_im2col_in", "a3d_unpack_out", "a3d_im2col_in_bwd")      # boundary kernels: the bf16 build has no suffix
 for _name in list(_SIGNATURES):
     if _name.endswith("_bf16"):
         _SIGNATURES[_name[:-5] + "_f16"] = _SIGNATURES[_name]
-    elif _name in ("a3d_im2col_in", "a3d_unpack_out"):
+    elif _name in _UNSUFFIXED_TWINS:
         _SIGNATURES[_name + "_f16"] = _SIGNATURES[_name]
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -180,7 +183,7 @@ class _Entry:
         if self._f16:
             if name.endswith("_bf16"):
                 name = name[:-5] + "_f16"
-            elif name in ("a3d_im2col_in", "a3d_unpack_out"):
+            elif name in _UNSUFFIXED_TWINS:
                 name = name + "_f16"
         return getattr(self._lib, name)
 
@@ -581,6 +584,27 @@ class HipOps:
         b = None if bias is None else bias.to(device=x.device, dtype=torch.float32).contiguous()
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
         _check(self.lib.a3d_channel_mix_f32(self._stream(), _p(x), _p(w), _p(b), _p(y), B, Cin, Cout, H * W, scale), "a3d_channel_mix_f32")
+        return y
+
+    # ---- VAE encoder input gradient (4D-SDS: vae_grad.py)
+    def im2col_in_bwd(self, dcol, V: int, C: int, F: int, H: int, W: int, scale: float = 1.0):
+        """Adjoint of ``im2col_in``: dCol [(V F) H W, 64] (storage type) -> fp32 [V, C, F, H, W] = scale * col2im(dCol)."""
+        dcol = self._act(dcol, "im2col_in_bwd.dcol")
+        assert dcol.is_contiguous() and dcol.shape == (V * F * H * W, 64)
+        dx = torch.empty((V, C, F, H, W), dtype=torch.float32, device=self.device)
+        _check(self.lib.a3d_im2col_in_bwd(self._stream(), _p(dcol), _p(dx), V, C, F, H, W, scale), f"a3d_im2col_in_bwd V={V} C={C} F={F} H={H} W={W}")
+        return dx
+
+    def softmax_rows_bwd(self, p, dp, alpha: float = 1.0, out=None):
+        """dS = alpha * P o (dP - rowsum(P o dP)) for probabilities ``p`` [M, N] (storage type, own row stride) and fp32 ``dp`` [M, N];
+        ``out``: [M, N] view with its own row stride."""
+        p = self._act(p, "softmax_rows_bwd.p")
+        assert dp.dtype == torch.float32 and dp.is_cuda and dp.stride(1) == 1 and dp.shape == p.shape
+        M, N = p.shape
+        y = self._act(out, "softmax_rows_bwd.out") if out is not None else self.empty(M, N)
+        assert y.shape == (M, N)
+        _check(self.lib.a3d_softmax_rows_bwd_bf16(self._stream(), _p(p), p.stride(0), _p(dp), dp.stride(0), _p(y), y.stride(0), M, N, alpha),
+               f"a3d_softmax_rows_bwd M={M} N={N}")
         return y
 
     # ---- training path: backward kernels (reference: torch autograd behind train.py:576-590) and the optimiser step

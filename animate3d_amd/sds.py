@@ -21,6 +21,7 @@ from __future__ import annotations
 from typing import Dict, Optional, Tuple
 
 import torch
+import torch.nn.functional as F
 
 from .denoise import ddim_schedule, randn_like_reference
 
@@ -95,3 +96,22 @@ def sds_recon_loss(unet, latents: torch.Tensor, t: torch.Tensor, text_embeddings
         recon = torch.cat([videos.detach().reshape(b * n, f, c, h, w)[:, :1], recon[:, 1:]], dim=1).reshape(b * n * f, c, h, w)
     loss = 0.5 * ((latents - recon) ** 2).sum() / latents.shape[0] * f / (f - 1)
     return loss, {"latents_noisy": noisy_flat, "noise_pred": eps_cfg, "latents_recon": recon}
+
+
+def sds_guidance_loss(vae, unet, rgb: torch.Tensor, t: torch.Tensor, text_embeddings: torch.Tensor, image_embeds: torch.Tensor,
+                      c2w: Optional[torch.Tensor], *, rgb_as_latents: bool = False, vae_generator: Optional[torch.Generator] = None,
+                      vae_noise: Optional[torch.Tensor] = None, **sds_kw) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """``AnimateMVDiffusionGuidance.__call__`` (animatemv_guidance.py:509-560) from the rendered frames to the loss, minus the CLIP image
+    encode (the caller passes ``image_embeds``: clip.py).  ``rgb`` [(b n f), H, W, 3] in [0, 1] -> bilinear resize to 256^2
+    (align_corners=False, :532-535) -> ``vae.encode_images`` (an ``AutoencoderKLEncoder``, :536-543) -> ``sds_recon_loss``.  With
+    ``rgb_as_latents`` (``rgb`` then has the 4 latent channels) the resize goes to 32^2 and the result is taken as the latents (:537-540).  ``vae_generator`` / ``vae_noise``: the
+    posterior sample's noise.  Returns (loss, aux) as ``sds_recon_loss`` does, with aux["latents"] the encoded latents;
+    ``loss.backward()`` fills ``rgb.grad`` through the encoder's input gradient."""
+    x = rgb.permute(0, 3, 1, 2)
+    if rgb_as_latents:
+        latents = F.interpolate(x, (32, 32), mode="bilinear", align_corners=False)
+    else:
+        latents = vae.encode_images(F.interpolate(x, (256, 256), mode="bilinear", align_corners=False), generator=vae_generator, noise=vae_noise)
+    loss, aux = sds_recon_loss(unet, latents, t.to(latents.device), text_embeddings, image_embeds, c2w, **sds_kw)
+    aux["latents"] = latents
+    return loss, aux

@@ -27,6 +27,7 @@ from typing import Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
+from .autograd_ops import AutogradOps
 from .denoise import randn_like_reference
 from .hip_ops import on_model_device
 
@@ -124,6 +125,32 @@ class _Encoder(nn.Module):
         self.conv_out = nn.Conv2d(boc[-1], 2 * cfg.latent_channels, 3, padding=1)
 
 
+def mid_attention(ops, x, B: int, L: int, pk, groups: int, keep: bool = False):
+    """diffusers Attention (AttnProcessor, one head of dim C, residual_connection=True) on the GroupNorm'ed tokens of B images of
+    L tokens.  ``keep``: also return (t, q, k), the operands the backward of vae_grad._VaeMidAttention reuses."""
+    C = x.shape[1]
+    t = ops.group_norm(x, B, L, pk.gn[0], pk.gn[1], groups, 1e-6, False)
+    q = ops.gemm(t, pk.q[0], pk.q[1])
+    k = ops.gemm(t, pk.k[0], pk.k[1])
+    a = ops.empty(B * L, C)
+    Lp = -(-L // 64) * 64                                # the P V contraction runs over L: the GEMM needs a multiple of 64
+    if Lp != L:                                          # other latent sizes: zero-padded P columns / V^T columns
+        p_pad, vt_pad = ops.empty(L, Lp).zero_(), ops.empty(C, Lp).zero_()
+    for b in range(B):                                   # per image: L x L logits in fp32, never rounded to bf16
+        rows = slice(b * L, (b + 1) * L)
+        s = ops.gemm_f32out(q[rows], k[rows], alpha=C ** -0.5)
+        if Lp == L:
+            p = ops.softmax_rows(s)
+            vt = ops.gemm(pk.v[0], t[rows])              # V^T [C, L] = W_v x^T (bias deferred: rows of P sum to 1)
+        else:
+            ops.softmax_rows(s, out=p_pad[:, :L])
+            ops.gemm(pk.v[0], t[rows], out=vt_pad[:, :L])
+            p, vt = p_pad, vt_pad
+        ops.gemm(p, vt, pk.v[1], out=a[rows])            # P V + b_v
+    out = ops.gemm(a, pk.o[0], pk.o[1], residual=x)
+    return (out, t, q, k) if keep else out
+
+
 class _VAEHalf(nn.Module):
     """What the two halves share: op-set plumbing, weight packing and the resnet / mid-attention forward pieces."""
 
@@ -200,8 +227,9 @@ class _VAEHalf(nn.Module):
                                n2=(self._f(r.norm2.weight), self._f(r.norm2.bias)), c2=self._conv_w(r.conv2), sc=sc)
 
     # ------------------------------------------------------------------ forward pieces (rows = [B*H*W, C] bf16)
-    def _resnet(self, x, B, H, W, pk):
-        ops, g = self.ops, self.config.norm_num_groups
+    # ``ops``: the op set to run on (default: the module's); the encoder's differentiable path passes a vae_grad.VaeGradOps
+    def _resnet(self, x, B, H, W, pk, ops=None):
+        ops, g = (self.ops if ops is None else ops), self.config.norm_num_groups
         h = ops.group_norm(x, B, H * W, pk.n1[0], pk.n1[1], g, 1e-6, True)
         h, _, _ = ops.conv3x3(h, B, H, W, pk.c1[0], pk.c1[1])
         h = ops.group_norm(h, B, H * W, pk.n2[0], pk.n2[1], g, 1e-6, True)
@@ -209,29 +237,12 @@ class _VAEHalf(nn.Module):
         out, _, _ = ops.conv3x3(h, B, H, W, pk.c2[0], pk.c2[1], residual=sc)
         return out
 
-    def _mid_attention(self, x, B, H, W, pk):
-        """diffusers Attention (AttnProcessor, one head of dim C, residual_connection=True) on the GroupNorm'ed tokens."""
-        ops, g = self.ops, self.config.norm_num_groups
-        L, C = H * W, x.shape[1]
-        t = ops.group_norm(x, B, L, pk.gn[0], pk.gn[1], g, 1e-6, False)
-        q = ops.gemm(t, pk.q[0], pk.q[1])
-        k = ops.gemm(t, pk.k[0], pk.k[1])
-        a = ops.empty(B * L, C)
-        Lp = -(-L // 64) * 64                                # the P V contraction runs over L: the GEMM needs a multiple of 64
-        if Lp != L:                                          # other latent sizes: zero-padded P columns / V^T columns
-            p_pad, vt_pad = ops.empty(L, Lp).zero_(), ops.empty(C, Lp).zero_()
-        for b in range(B):                                   # per image: L x L logits in fp32, never rounded to bf16
-            rows = slice(b * L, (b + 1) * L)
-            s = ops.gemm_f32out(q[rows], k[rows], alpha=C ** -0.5)
-            if Lp == L:
-                p = ops.softmax_rows(s)
-                vt = ops.gemm(pk.v[0], t[rows])              # V^T [C, L] = W_v x^T (bias deferred: rows of P sum to 1)
-            else:
-                ops.softmax_rows(s, out=p_pad[:, :L])
-                ops.gemm(pk.v[0], t[rows], out=vt_pad[:, :L])
-                p, vt = p_pad, vt_pad
-            ops.gemm(p, vt, pk.v[1], out=a[rows])            # P V + b_v
-        return ops.gemm(a, pk.o[0], pk.o[1], residual=x)
+    def _mid_attention(self, x, B, H, W, pk, ops=None):
+        ops = self.ops if ops is None else ops
+        differentiable = getattr(ops, "vae_mid_attention", None)         # vae_grad.VaeGradOps: one autograd node for the whole block
+        if differentiable is not None:
+            return differentiable(x, B, H * W, pk, self.config.norm_num_groups)
+        return mid_attention(ops, x, B, H * W, pk, self.config.norm_num_groups)
 
 
 class AutoencoderKLDecoder(_VAEHalf):
@@ -308,6 +319,7 @@ class AutoencoderKLEncoder(_VAEHalf):
         with (torch.device(device) if device is not None else torch.device("cpu")):
             self.encoder = _Encoder(cfg)
             self.quant_conv = nn.Conv2d(2 * cfg.latent_channels, 2 * cfg.latent_channels, 1)
+        self._gops = None            # vae_grad.VaeGradOps over self.ops (encode_images with autograd)
 
     def _pack(self):
         e, cfg = self.encoder, self.config
@@ -337,43 +349,71 @@ class AutoencoderKLEncoder(_VAEHalf):
         self._packed = P
         return P
 
-    def _downsample(self, x, B, H, W, pk):
+    def _downsample(self, x, B, H, W, pk, ops):
         """Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) then conv3x3 stride 2 == flip(conv3x3_s2_p1(flip(x), flip(w)))."""
         if H % 2 or W % 2:
             raise ValueError(f"VAE encoder needs even feature maps at every level, got {H}x{W}")
         C = x.shape[1]
         xf = x.reshape(B, H, W, C).flip(1, 2).reshape(B * H * W, C).contiguous()
-        y, Ho, Wo = self.ops.conv3x3(xf, B, H, W, pk[0], pk[1], stride=2)
+        y, Ho, Wo = ops.conv3x3(xf, B, H, W, pk[0], pk[1], stride=2)
         Co = y.shape[1]
         return y.reshape(B, Ho, Wo, Co).flip(1, 2).reshape(B * Ho * Wo, Co).contiguous(), Ho, Wo
+
+    def _check_images(self, images: torch.Tensor):
+        cfg = self.config
+        B, Ci, H, W = images.shape
+        levels = len(cfg.block_out_channels) - 1
+        if Ci != cfg.out_channels or H % (1 << levels) or W % (1 << levels):
+            raise ValueError(f"images must be [B, {cfg.out_channels}, H, W] with H, W multiples of {1 << levels}")
+
+    def _moments(self, ops, images: torch.Tensor, unit_range: bool = False) -> torch.Tensor:
+        """Encoder + quant_conv: fp32 moments [B, 8, H/8, W/8] of images [B, 3, H, W] in [-1, 1] — or in [0, 1] with ``unit_range``
+        (``ops.im2col_images`` then folds the ``* 2 - 1`` into conv_in's operand and its adjoint)."""
+        cfg = self.config
+        self._check_images(images)
+        P = self._packed if self._packed is not None else self._pack()
+        B, Ci, H, W = images.shape
+        if unit_range:
+            cols = ops.im2col_images(images, self.device)
+        else:
+            img = images.to(device=self.device, dtype=torch.float32).contiguous()
+            cols = ops.im2col_in(img.reshape(B, Ci, 1, H, W))
+        x = ops.gemm(cols, P.conv_in[0], P.conv_in[1])
+        for blk in P.down:
+            for r in blk.res:
+                x = self._resnet(x, B, H, W, r, ops)
+            if blk.down is not None:
+                x, H, W = self._downsample(x, B, H, W, blk.down, ops)
+        x = self._resnet(x, B, H, W, P.mid.r0, ops)
+        x = self._mid_attention(x, B, H, W, P.mid, ops)
+        x = self._resnet(x, B, H, W, P.mid.r1, ops)
+        x = ops.group_norm(x, B, H * W, P.norm_out[0], P.norm_out[1], cfg.norm_num_groups, 1e-6, True)
+        x, _, _ = ops.conv3x3(x, B, H, W, P.conv_out[0], P.conv_out[1])
+        c2 = 2 * cfg.latent_channels
+        moments = ops.unpack_out(x, B, c2, 1, H, W, torch.float32)[:, :, 0].contiguous()
+        return ops.channel_mix(moments, P.quant[0], P.quant[1], 1.0)             # quant_conv (1x1) in fp32
+
+    def _grad_ops(self):
+        """The differentiable op set over this module's kernels (built once per op set)."""
+        from .vae_grad import VaeGradOps
+        base = self._plain_ops()
+        if self._gops is None or self._gops.base is not base:
+            self._gops = VaeGradOps(base)
+        return self._gops
+
+    def _plain_ops(self):
+        """The kernels themselves: the base of a differentiable op set handed to the constructor (its autograd forms are not needed
+        where nothing requires a gradient, and it has none for the mid-block attention's pieces)."""
+        return self.ops.base if isinstance(self.ops, AutogradOps) else self.ops
 
     @torch.no_grad()
     @on_model_device
     def encode(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """AutoencoderKL.encode(x).latent_dist for x [B, 3, H, W] in [-1, 1]: (mean, logvar) fp32 [B, 4, H/8, W/8], logvar
         clamped to [-30, 20] as DiagonalGaussianDistribution does."""
-        ops, cfg = self.ops, self.config
-        P = self._packed if self._packed is not None else self._pack()
-        B, Ci, H, W = images.shape
-        levels = len(cfg.block_out_channels) - 1
-        if Ci != cfg.out_channels or H % (1 << levels) or W % (1 << levels):
-            raise ValueError(f"images must be [B, {cfg.out_channels}, H, W] with H, W multiples of {1 << levels}")
-        img = images.to(device=self.device, dtype=torch.float32).contiguous()
-        x = ops.gemm(ops.im2col_in(img.reshape(B, Ci, 1, H, W)), P.conv_in[0], P.conv_in[1])
-        for blk in P.down:
-            for r in blk.res:
-                x = self._resnet(x, B, H, W, r)
-            if blk.down is not None:
-                x, H, W = self._downsample(x, B, H, W, blk.down)
-        x = self._resnet(x, B, H, W, P.mid.r0)
-        x = self._mid_attention(x, B, H, W, P.mid)
-        x = self._resnet(x, B, H, W, P.mid.r1)
-        x = ops.group_norm(x, B, H * W, P.norm_out[0], P.norm_out[1], cfg.norm_num_groups, 1e-6, True)
-        x, _, _ = ops.conv3x3(x, B, H, W, P.conv_out[0], P.conv_out[1])
-        c2 = 2 * cfg.latent_channels
-        moments = ops.unpack_out(x, B, c2, 1, H, W, torch.float32)[:, :, 0].contiguous()
-        moments = ops.channel_mix(moments, P.quant[0], P.quant[1], 1.0)             # quant_conv (1x1) in fp32
-        mean, logvar = moments[:, : cfg.latent_channels], moments[:, cfg.latent_channels:]
+        moments = self._moments(self.ops, images)
+        lc = self.config.latent_channels
+        mean, logvar = moments[:, :lc], moments[:, lc:]
         return mean.contiguous(), logvar.clamp(-30.0, 20.0).contiguous()
 
     @torch.no_grad()
@@ -382,3 +422,24 @@ class AutoencoderKLEncoder(_VAEHalf):
         mean, logvar = self.encode(images)
         noise = randn_like_reference(mean.shape, generator, mean.device, mean.dtype)
         return (mean + torch.exp(0.5 * logvar) * noise) * self.config.scaling_factor
+
+    @on_model_device
+    def encode_images(self, imgs: torch.Tensor, generator: Optional[torch.Generator] = None,
+                      noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 4D-SDS guidance's ``encode_images`` (animatemv_guidance.py:365-373): imgs [B, 3, H, W] in [0, 1] ->
+        ``vae.encode(imgs * 2 - 1).latent_dist.sample() * scaling_factor`` [B, 4, H/8, W/8] in ``imgs.dtype``.  Differentiable with
+        respect to ``imgs`` when grad is enabled and ``imgs`` requires it (the SDS loss reaches the renderer only through this call);
+        the weights stay frozen.  Same forward kernels as ``encode``: the moments are bit-identical to ``encode(imgs * 2 - 1)``.
+        ``noise`` [B, 4, H/8, W/8] replaces the draw from ``generator``."""
+        if torch.is_grad_enabled() and imgs.requires_grad:
+            moments = self._moments(self._grad_ops(), imgs, unit_range=True)
+        else:
+            with torch.no_grad():
+                moments = self._moments(self._plain_ops(), imgs * 2 - 1)
+        lc = self.config.latent_channels
+        mean, logvar = moments[:, :lc].contiguous(), moments[:, lc:].clamp(-30.0, 20.0).contiguous()
+        if noise is None:
+            noise = randn_like_reference(mean.shape, generator, mean.device, mean.dtype)
+        else:
+            noise = noise.to(device=mean.device, dtype=mean.dtype)
+        return ((mean + torch.exp(0.5 * logvar) * noise) * self.config.scaling_factor).to(imgs.dtype)

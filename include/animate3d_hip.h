@@ -246,12 +246,24 @@ int a3d_timestep_embed_bf16(a3d_stream_t stream, const float* t, void* Y, int V,
  * permute/reshape of unet_motion_mv_model.py:767 and conv_in's patch gather. 9*C <= 64. */
 int a3d_im2col_in(a3d_stream_t stream, const void* sample, int dtype, void* Y, int V, int C, int F, int H, int W);
 
+/* Adjoint of a3d_im2col_in: dCol rows [(V F) H W, 64] bf16 (columns k >= 9*C ignored) -> fp32 dX [V, C, F, H, W] =
+ * scale * col2im(dCol).  The input gradient of conv_in on the fp32 RGB image of the VAE encoder (4D-SDS,
+ * animatemv_guidance.py:365-373); `scale` folds the 2 of imgs * 2 - 1 and the removal of a gradient scale.  9*C <= 64. */
+int a3d_im2col_in_bwd(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale);
+
 /* rows [(V F) H W, C] bf16 -> [V, C, F, H, W] in `dtype` (unet_motion_mv_model.py:862). */
 int a3d_unpack_out(a3d_stream_t stream, const void* X, void* Y, int dtype, int V, int C, int F, int H, int W);
 
 /* Row softmax of fp32 logits X[M, N] (row stride ldx floats) -> bf16 probabilities Y[M, N] (row stride ldy elements);
  * the softmax of diffusers' AttnProcessor in the VAE mid block.  N % 4 == 0. */
 int a3d_softmax_rows_f32_bf16(a3d_stream_t stream, const float* X, int64_t ldx, void* Y, int64_t ldy, int64_t M, int64_t N);
+
+/* Backward of a3d_softmax_rows_f32_bf16 (the VAE encoder's mid-block attention on the 4D-SDS input-gradient path):
+ *   dS[m, n] = alpha * P[m, n] * (dP[m, n] - sum_j P[m, j] dP[m, j])
+ * with P the bf16 probabilities the forward multiplied by V (row stride ldp elements), dP fp32 (row stride lddp floats), dS bf16 (row
+ * stride ldds elements); the row sum is fp32.  N % 4 == 0, ldp / lddp / ldds multiples of 4 and >= N, P / dS 8-byte and dP 16-byte aligned. */
+int a3d_softmax_rows_bwd_bf16(a3d_stream_t stream, const void* P, int64_t ldp, const float* dP, int64_t lddp, void* dS, int64_t ldds,
+                              int64_t M, int64_t N, float alpha);
 
 /* Planar fp32 channel mix y[b, o, :] = scale * sum_c w[o, c] x[b, c, :] + bias[o] for <= 8 channels: the VAE's 1x1
  * post_quant_conv together with the 1 / scaling_factor of pipeline.py:567 (decode_latents). */
@@ -369,7 +381,7 @@ int a3d_adamw_f32(a3d_stream_t stream, float* p, const float* g, float* m, float
  * v_mfma_f32_32x32x16_f16): the dtype the reference's 4D-SDS caller runs the UNet in (animatemv_guidance.py:339-346 casts
  * the model and every input to fp16; BASELINE.json configs 4 and 5).  Built from the same sources with -DA3D_STORAGE_F16
  * (animate3d_amd/build.py).  a3d_im2col_in_f16 / a3d_unpack_out_f16: the CALLER tensor's dtype is still the `dtype` argument,
- * the activation side is fp16.
+ * the activation side is fp16; a3d_im2col_in_bwd_f16 reads fp16 dCol rows and still writes fp32.
  * --------------------------------------------------------------------------------------------------------------------- */
 int a3d_gemm_f16(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                   const float* bias, const void* rowbias, int64_t rb_div, const void* R, int64_t ldr,
@@ -429,6 +441,9 @@ int a3d_timestep_embed_f16(a3d_stream_t stream, const float* t, void* Y, int V, 
 int a3d_im2col_in_f16(a3d_stream_t stream, const void* sample, int dtype, void* Y, int V, int C, int F, int H, int W);
 int a3d_unpack_out_f16(a3d_stream_t stream, const void* X, void* Y, int dtype, int V, int C, int F, int H, int W);
 int a3d_softmax_rows_f32_f16(a3d_stream_t stream, const float* X, int64_t ldx, void* Y, int64_t ldy, int64_t M, int64_t N);
+int a3d_softmax_rows_bwd_f16(a3d_stream_t stream, const void* P, int64_t ldp, const float* dP, int64_t lddp, void* dS, int64_t ldds,
+                             int64_t M, int64_t N, float alpha);
+int a3d_im2col_in_bwd_f16(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale);
 int a3d_flash_attn_bwd_f16(a3d_stream_t stream, const void* Q, const void* K, const void* V, const void* dO,
                             void* dQ, void* dK, void* dV, float* lse2, float* delta,
                             const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* domap,

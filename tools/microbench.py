@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """In-process A/B micro-benchmarks of the dominant kernels on one MI355X (HIP events on the launch stream,
-interleaved rounds, median reported).  Usage:  python tools/microbench.py [flash] [gemm] [conv] [misc]"""
+interleaved rounds, median reported).  Usage:  python tools/microbench.py [flash] [gemm] [conv] [misc] [sdsgrad] ..."""
 import os
 import statistics
 import sys
@@ -487,6 +487,110 @@ def bench_vae(ops):
               f"peak mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
 
+def bench_sdsgrad(_ops):
+    """BASELINE config 5 as one 4D-SDS optimisation step runs it (animatemv_guidance.py:509-560): 64 rendered images of 256^2 (b = 1,
+    4 views x 16 frames) -> VAE encode with autograd -> UNet call (synthetic weights) -> loss.backward() into the pixels, in fp16 (the
+    reference's weights_dtype) and bf16 storage.  Encoder forward / backward timed on their own (HIP events, median of 5 after one warm-up),
+    the UNet call as sds_recon_loss on given latents (no_grad inside, as the reference's), the whole step, peak memory of the step; then the
+    stride-2 dgrad of the three downsamplers (a3d_zero_insert2x + stride-1 conv, autograd_ops._Conv3x3) alone at the step's shapes."""
+    from animate3d_amd.autograd_ops import AutogradOps
+    from animate3d_amd.config import UNetConfig
+    from animate3d_amd.sds import sds_guidance_loss, sds_recon_loss
+    from animate3d_amd.unet import MVUNetMotionModel
+    from animate3d_amd.vae import AutoencoderKLEncoder
+    n, f, N = 4, 16, 64
+
+    def med(fn, reps=5):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            ts.append(fn())
+        return statistics.median(ts)
+
+    def ev():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    for dt in (torch.float16, torch.bfloat16):
+        name = str(dt)[6:]
+        torch.cuda.empty_cache()
+        enc = AutoencoderKLEncoder(device="cuda").init_synthetic(seed=0).to(dt).eval()
+        unet = MVUNetMotionModel(UNetConfig(), num_views=n, device="cuda")
+        unet.init_synthetic(seed=0)
+        unet = unet.to(dt).eval()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        rgb = torch.rand(N, 256, 256, 3, device="cuda", generator=g).requires_grad_(True)
+        imgs = rgb.detach().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+        vn = torch.randn(N, 4, 32, 32, device="cuda", generator=g)
+        cot = torch.randn(N, 4, 32, 32, device="cuda", generator=g) * 1e-2
+        t = torch.tensor([500], device="cuda")
+        text = torch.randn(2 * n, 77, 768, device="cuda", generator=g)
+        emb = torch.randn(n, 1024, device="cuda", generator=g)
+        c2w = torch.eye(4, device="cuda").repeat(N, 1, 1)
+        c2w[:, :3, 3] = torch.randn(N, 3, device="cuda", generator=g) * 2
+        kw = dict(n_view=n, n_frame=f, weights_dtype=dt)
+        split = {}
+
+        def enc_fb():
+            imgs.grad = None
+            e0 = ev(); lat = enc.encode_images(imgs, noise=vn); e1 = ev(); lat.backward(cot); e2 = ev()
+            torch.cuda.synchronize()
+            split.setdefault("f", []).append(e0.elapsed_time(e1)); split.setdefault("b", []).append(e1.elapsed_time(e2))
+            return e0.elapsed_time(e2)
+
+        def enc_fwd_nograd():
+            e0 = ev()
+            with torch.no_grad():
+                enc.encode_images(imgs.detach(), noise=vn)
+            e1 = ev(); torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        lat0 = enc.encode_images(imgs.detach(), noise=vn)
+
+        def unet_call():
+            e0 = ev(); sds_recon_loss(unet, lat0, t, text, emb, c2w, **kw); e1 = ev(); torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        def step():
+            rgb.grad = None
+            e0 = ev(); loss, _ = sds_guidance_loss(enc, unet, rgb, t, text, emb, c2w, vae_noise=vn, **kw); loss.backward(); e1 = ev()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        t_inf = med(enc_fwd_nograd)
+        med(enc_fb)
+        tf, tb = statistics.median(split["f"][1:]), statistics.median(split["b"][1:])
+        t_unet = med(unet_call)
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        t_step = med(step)
+        peak = torch.cuda.max_memory_allocated() / 2 ** 30
+        print(f"== sdsgrad {name}: {N} images 256^2 -> 32^2 latents (b = 1, {n} views x {f} frames)")
+        print(f"   encoder forward, no grad (encode_images)     : {t_inf:8.2f} ms")
+        print(f"   encoder forward with autograd                : {tf:8.2f} ms")
+        print(f"   encoder backward (input gradient)            : {tb:8.2f} ms   = {tb / tf:4.2f} x the forward with autograd")
+        print(f"   UNet call (sds_recon_loss on given latents)  : {t_unet:8.2f} ms")
+        print(f"   sds_guidance_loss + loss.backward()          : {t_step:8.2f} ms   peak memory {peak:6.2f} GiB")
+        aops = AutogradOps(enc.ops)
+        tot = 0.0
+        for (H, C) in ((256, 128), (128, 256), (64, 512)):
+            Ho = H // 2
+            x = torch.randn(N * H * H, C, device="cuda").to(dt).requires_grad_(True)
+            w = (torch.randn(C, 9 * C, device="cuda") * (9 * C) ** -0.5).to(dt)
+            y, _, _ = aops.conv3x3(x, N, H, H, w, None, stride=2)
+            dy = torch.randn(N * Ho * Ho, C, device="cuda").to(dt)
+
+            def bwd():
+                e0 = ev(); torch.autograd.grad(y, x, dy, retain_graph=True); e1 = ev(); torch.cuda.synchronize()
+                return e0.elapsed_time(e1)
+            tt = med(bwd)
+            tot += tt
+            print(f"   stride-2 dgrad {H}x{H} C={C} (zero insert + conv): {tt:8.2f} ms")
+        print(f"   stride-2 dgrad, three downsamplers            : {tot:8.2f} ms   = {100 * tot / tb:4.1f} % of the encoder backward")
+        del enc, unet, lat0
+
+
 def bench_misc(ops):
     print("== memory-bound kernels at level 0 ([524288, 320] tokens); median ms / effective GB/s (algorithmic bytes)")
     M, C, V, F, L = 524288, 320, 8, 16, 4096
@@ -514,7 +618,7 @@ if __name__ == "__main__":
     ops = HipOps()
     print(torch.cuda.get_device_name(0))
     for w in which:
-        {"flash": bench_flash, "vae": bench_vae, "loop": bench_loop, "graph": bench_graph, "gemm": bench_gemm, "conv": bench_conv, "misc": bench_misc,
+        {"flash": bench_flash, "vae": bench_vae, "sdsgrad": bench_sdsgrad, "loop": bench_loop, "graph": bench_graph, "gemm": bench_gemm, "conv": bench_conv, "misc": bench_misc,
          "flashdm": bench_flashdm, "smallm": bench_smallm, "gn": bench_gn, "onewave": bench_onewave, "shortk": bench_shortk, "directepi": bench_directepi, "flashspread": bench_flashspread, "flashdt": bench_flashdt, "flashrank": bench_flashrank, "gemmscale": bench_gemmscale, "gemmcal": bench_gemmcal, "wgrad": bench_wgrad, "attnbwd": bench_attnbwd, "flash16": bench_flash16,
          "flash40": lambda o: bench_flash(o, ((40, 4, 16, 4096, 2),)),
          "flashshort": lambda o: bench_flash(o, ((80, 4, 16, 256, 2), (80, 4, 16, 128, 2), (80, 4, 16, 512, 2), (80, 1, 16, 1024, 2), (40, 4, 16, 256, 2), (40, 4, 16, 64, 2), (160, 4, 16, 256, 2), (160, 4, 16, 64, 2))),
