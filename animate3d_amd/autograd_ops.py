@@ -102,7 +102,8 @@ def deferred_param_grads():
     """Around ``loss.backward()`` of a loop that owns its gradient buffers (``train.training_step`` with ``FlatAdamW``): the fp32 gradient
     slices that ``PackW.backward`` would hand to autograd's AccumulateGrad nodes — one small ``grad.add_`` launch per trainable weight, ~850 per
     step in the reference's configuration, launch-bound — are parked and added to the parameters' ``.grad`` in ONE multi-tensor call when
-    the backward pass is over.  Not for loops that hang hooks on gradient accumulation (torch DDP): leave those on the plain path."""
+    the backward pass is over.  Not for loops that hang hooks on gradient accumulation (torch DDP): leave those on the plain path.
+    If the backward raises inside the block, the parked slices are dropped and the parameters' ``.grad`` is undefined afterwards."""
     st = _Deferred
     prev, st.active = st.active, True
     try:

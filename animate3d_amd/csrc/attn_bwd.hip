@@ -21,6 +21,9 @@
 // one or two 32-column sub-tiles (CT) that share every row-side LDS fragment.
 #include "common.h"
 
+#include <cfloat>
+#include <cmath>
+
 namespace {
 
 constexpr int MODE_DQ = 0, MODE_DKV = 1, MODE_STATS = 2;
@@ -32,6 +35,7 @@ struct BwdParams {
   a3d_rowmap qm, km, dom, dqm, dkm;       // rows of Q, K|V, dO, dQ, dK|dV
   int heads; int q_len, kv_len; int q_per_kv;
   float scale, scale_log2, do_scale; int accumulate;
+  float inv_do_scale;                     // 1 / do_scale, 0 for do_scale == 0 (the gradients vanish: no -0 * inf seed)
 };
 
 A3D_DEV int64_t map_row(const a3d_rowmap& m, int64_t g, int64_t s) {
@@ -196,7 +200,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
   const int total_tiles = ntiles * ((MODE == MODE_DKV) ? p.q_per_kv : 1);
   u32x4_t n1[NPT], n2[NPT];
   float stat_r = 0.f;
-  const float inv_do_scale = 1.f / p.do_scale;
+  const float inv_do_scale = p.inv_do_scale;
   auto load_tile = [&](int t) __attribute__((always_inline)) {
     const int64_t grp_r = (MODE == MODE_DKV) ? grp_c + t / ntiles : grp_c;      // group the row maps see
     const int r0 = (t % ntiles) * BR;
@@ -565,6 +569,10 @@ extern "C" int A3D_FN(a3d_flash_attn_bwd)(a3d_stream_t stream, const void* Q, co
   if (!map_ok(qmap, head_dim, heads) || !map_ok(kmap, head_dim, heads) || !map_ok(domap, head_dim, heads)) return A3D_EINVAL;
   if (dQ && !map_ok(dqmap, head_dim, heads)) return A3D_EINVAL;
   if (dK && !map_ok(dkmap, head_dim, heads)) return A3D_EINVAL;
+  // the staging loads and gradient stores are 16 bytes wide (rows: ld % 8 == 0 above), the statistics fp32 scalars
+  if (!a3d_aligned(16, Q, K, V, dO, dQ, dK, dV) || !a3d_aligned(4, lse2, delta)) return A3D_EINVAL;
+  // dP starts at -delta / do_scale: a zero do_scale is exact (zero gradients), a subnormal or non-finite one has no usable reciprocal
+  if (!std::isfinite(do_scale) || (do_scale != 0.f && std::fabs(do_scale) < FLT_MIN)) return A3D_EINVAL;
   BwdParams p;
   p.Q = (const uint16_t*)Q; p.K = (const uint16_t*)K; p.V = (const uint16_t*)V; p.dO = (const uint16_t*)dO;
   p.dQ = (uint16_t*)dQ; p.dK = (uint16_t*)dK; p.dV = (uint16_t*)dV;
@@ -575,10 +583,13 @@ extern "C" int A3D_FN(a3d_flash_attn_bwd)(a3d_stream_t stream, const void* Q, co
   // accumulate: bit 0 = add to dQ / dK / dV; bit 1 = lse2 and delta hold the statistics already (a3d_flash_attn_lse + a3d_attn_delta):
   // the statistics pass (a third of the backward's time at head_dim 40) is skipped
   p.scale = scale; p.scale_log2 = scale * 1.4426950408889634f; p.do_scale = do_scale; p.accumulate = accumulate & 1;
+  p.inv_do_scale = do_scale != 0.f ? 1.f / do_scale : 0.f;
   hipStream_t s = (hipStream_t)stream;
   if (!((accumulate >> 1) & 1)) {
     if (int rc = dispatch<MODE_STATS>(s, p, head_dim, groups)) return rc;
   }
+  // do_scale == 0 adds nothing: accumulated buffers stay bit for bit as they are (lse2 / delta are still written above for a later call)
+  if (do_scale == 0.f && p.accumulate) return A3D_OK;
   if (dQ) { if (int rc = dispatch<MODE_DQ>(s, p, head_dim, groups)) return rc; }
   if (dK) { if (int rc = dispatch<MODE_DKV>(s, p, head_dim, groups / q_per_kv)) return rc; }
   return A3D_OK;
@@ -588,7 +599,7 @@ extern "C" int A3D_FN(a3d_attn_delta)(a3d_stream_t stream, const void* dO, const
                                        float* delta, int groups, int heads, int head_dim, int64_t q_len) {
   if (!dO || !O || !delta || groups <= 0 || groups > 65535 || heads <= 0 || q_len <= 0 || q_len > 0x7fffffffLL) return A3D_EINVAL;
   if (!map_ok(domap, head_dim, heads) || !map_ok(omap, head_dim, heads)) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(dO) | reinterpret_cast<uintptr_t>(O)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, dO, O) || !a3d_aligned(4, delta)) return A3D_EINVAL;
   const int64_t n = q_len * heads;
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)groups);
   hipStream_t s = (hipStream_t)stream;

@@ -136,3 +136,10 @@ static inline int a3d_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? A3D_OK : (int)e;
 }
+
+// Entry-point precondition: every pointer is a multiple of `bytes` (a power of two: the widest access the kernels make through it).
+// NULL passes: whether an optional operand may be absent is checked on its own.
+template <typename... P>
+static inline bool a3d_aligned(uintptr_t bytes, const P*... ptrs) {
+  return ((reinterpret_cast<uintptr_t>(ptrs) | ... | uintptr_t(0)) & (bytes - 1)) == 0;
+}

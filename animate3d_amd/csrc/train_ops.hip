@@ -714,13 +714,14 @@ extern "C" int A3D_FN(a3d_colsum)(a3d_stream_t stream, const void* X, int64_t ld
 
 extern "C" int A3D_FN(a3d_geglu_bwd)(a3d_stream_t stream, const void* P, int64_t ldp, const void* dY, int64_t lddy, void* dP, int64_t lddp, int64_t M, int64_t N) {
   if (!P || !dY || !dP || M <= 0 || N <= 0 || N % 32 != 0 || ldp % 8 || lddy % 8 || lddp % 8) return A3D_EINVAL;
+  if (!a3d_aligned(16, P, dY, dP)) return A3D_EINVAL;
   const int64_t n = M * (N / 8);
   geglu_bwd_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)P, ldp, (const uint16_t*)dY, lddy, (uint16_t*)dP, lddp, M, N);
   return a3d_launch_status();
 }
 
 extern "C" int A3D_FN(a3d_axpby)(a3d_stream_t stream, const void* X, void* Y, int64_t n, float a, float b) {
-  if (!X || !Y || n <= 0 || n % 8 != 0) return A3D_EINVAL;
+  if (!X || !Y || n <= 0 || n % 8 != 0 || !a3d_aligned(16, X, Y)) return A3D_EINVAL;
   axpby_kernel<<<dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)X, (uint16_t*)Y, n / 8, a, b);
   return a3d_launch_status();
 }
@@ -753,6 +754,7 @@ extern "C" int A3D_FN(a3d_group_norm_bwd)(a3d_stream_t stream, const void* X, co
   if (!X || !dY || !gamma || !beta || !stats || !dX || !ws || B <= 0 || rows <= 0 || C <= 0 || groups <= 0 || groups > 64 || C % groups != 0 || C % 8 != 0)
     return A3D_EINVAL;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, dY, dX) || !a3d_aligned(4, gamma, beta, stats, ws, dgamma, dbeta)) return A3D_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * C * 2 * sizeof(float), s); e != hipSuccess) return (int)e;
   GNBParams p{(const uint16_t*)X, (const uint16_t*)dY, gamma, beta, stats, (uint16_t*)dX, ws, dgamma, dbeta, B, rows, C, groups, C / groups, silu, 0};
@@ -773,7 +775,7 @@ extern "C" int A3D_FN(a3d_group_norm_bwd)(a3d_stream_t stream, const void* X, co
 }
 
 extern "C" int A3D_FN(a3d_zero_insert2x)(a3d_stream_t stream, const void* dY, void* Z, int B, int H, int W, int C) {
-  if (!dY || !Z || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0) return A3D_EINVAL;
+  if (!dY || !Z || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !a3d_aligned(16, dY, Z)) return A3D_EINVAL;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int64_t n = (int64_t)B * H * W * (C / 8);
   zero_insert_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)dY, (uint16_t*)Z, B, H, W, Ho, Wo, C);
@@ -781,7 +783,7 @@ extern "C" int A3D_FN(a3d_zero_insert2x)(a3d_stream_t stream, const void* dY, vo
 }
 
 extern "C" int A3D_FN(a3d_upsample2x_bwd)(a3d_stream_t stream, const void* dU, void* dX, int B, int H, int W, int He, int We, int C) {
-  if (!dU || !dX || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0) return A3D_EINVAL;
+  if (!dU || !dX || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !a3d_aligned(16, dU, dX)) return A3D_EINVAL;
   if ((He != 2 * H && He != 2 * H - 1) || (We != 2 * W && We != 2 * W - 1)) return A3D_EINVAL;
   const int64_t n = (int64_t)B * H * W * (C / 8);
   upsample_bwd_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)dU, (uint16_t*)dX, B, H, W, He, We, C);
@@ -794,6 +796,7 @@ extern "C" int A3D_FN(a3d_temporal_attn_bwd)(a3d_stream_t stream, const void* Q,
   if (!Q || !K || !V || !dO || !dQ || !dK || !dV || videos <= 0 || frames <= 0 || frames > 32 || L <= 0 || heads <= 0) return A3D_EINVAL;
   const int C = heads * head_dim;
   if (C % SLAB != 0 || ldqkv % 8 || lddo % 8 || ldd % 8 || ldqkv < C || lddo < C || ldd < C) return A3D_EINVAL;
+  if (!a3d_aligned(16, Q, K, V, dO, dQ, dK, dV)) return A3D_EINVAL;
   TABParams p{(const uint16_t*)Q, (const uint16_t*)K, (const uint16_t*)V, ldqkv, (const uint16_t*)dO, lddo,
               (uint16_t*)dQ, (uint16_t*)dK, (uint16_t*)dV, ldd, frames, L, scale, scale * 1.4426950408889634f, (int64_t)videos * L};
   hipStream_t s = (hipStream_t)stream;

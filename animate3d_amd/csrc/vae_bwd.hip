@@ -82,6 +82,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const uint16_t* P
 
 extern "C" int A3D_IM2COL_IN_BWD(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale) {
   if (!dCol || !dX || V <= 0 || C <= 0 || F <= 0 || H <= 0 || W <= 0 || 9 * C > 64) return A3D_EINVAL;
+  if (!a3d_aligned(2, dCol) || !a3d_aligned(4, dX)) return A3D_EINVAL;
   im2col_in_bwd_kernel<<<grid_for((int64_t)V * C * F * H * W), 256, 0, (hipStream_t)stream>>>((const uint16_t*)dCol, dX, V, C, F, H, W, scale);
   return a3d_launch_status();
 }

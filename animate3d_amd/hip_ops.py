@@ -227,13 +227,20 @@ class HipOps:
         # overflow of the max-free pass, [2] workgroups launched.  None (default): the plain entry point.
         self.attn_counters = None
         self._ws_plan = {}           # launch shape -> split-K workspace bytes (0: the shape does not split)
-        self._ws_buf = None          # ONE split-K workspace per op set, grown to the largest need (launches on one stream run in order,
-                                     # so consecutive split launches may share it; a fresh 100-MB torch.empty per call was the alternative)
+        self._ws_bufs = {}           # stream handle -> ONE split-K workspace per stream, grown to the largest need (launches on one stream
+                                     # run in order, so consecutive split launches may share it; a fresh 100-MB torch.empty per call was the
+                                     # alternative).  Per stream: two streams sharing one buffer would overwrite each other's partials.
 
     def _workspace(self, need: int) -> torch.Tensor:
-        if self._ws_buf is None or self._ws_buf.numel() < need:
-            self._ws_buf = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
-        return self._ws_buf
+        if torch.cuda.is_current_stream_capturing():
+            # a captured graph keeps the pointer for every replay: a buffer of its own, from the graph's private pool, that lives as long as
+            # the graph — the eager buffer may be regrown (and its memory handed to another tensor) after the capture
+            return torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
+        stream = self._stream()
+        buf = self._ws_bufs.get(stream)
+        if buf is None or buf.numel() < need:
+            buf = self._ws_bufs[stream] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
+        return buf
 
     def _gemm_flags(self, tile128: bool, ring: bool = False, direct: bool = False) -> int:
         r = int(self.reserved_cus)
@@ -610,13 +617,14 @@ class HipOps:
     # ---- training path: backward kernels (reference: torch autograd behind train.py:576-590) and the optimiser step
     def flash_attn_bwd(self, q, k, v, do, qmap: RowMap, kmap: RowMap, groups: int, heads: int, q_len: int, kv_len: int, *,
                        q_per_kv: int = 1, do_scale: float = 1.0, need_dq: bool = True, need_dkv: bool = True, o=None, lse=None,
-                       dq_out=None, dk_out=None, dv_out=None):
+                       dq_out=None, dk_out=None, dv_out=None, accumulate: bool = False):
         """Gradients of ``flash_attn`` (same maps): ``do`` = gradient of the output buffer (rows as q), scaled by ``do_scale`` (= the
         forward's out_scale).  Returns (dq [q rows, C] | None, dk, dv [k rows, C] | None); rows of dk / dv that the K/V map never
         reads (e.g. frames > 0 in the first-frame branch) are zero.  ``o`` / ``lse`` (the un-accumulated output and the log-sum-exp of
         ``flash_attn(with_lse=True)``): the statistics pass is replaced by one elementwise kernel (delta = rowsum(dO * O) per head).
         ``dq_out`` / ``dk_out`` + ``dv_out``: [rows, C] views with their own row stride (the column blocks of the gradient of a fused
-        Q|K|V projection output) that the kernel writes instead of fresh tensors; they are returned."""
+        Q|K|V projection output) that the kernel writes instead of fresh tensors; they are returned.  ``accumulate``: the gradients are
+        ADDED to those views (every wanted gradient needs one); ``do_scale`` 0 then leaves them bit for bit as they were."""
         q, k, v, do = self._act(q, "attn_bwd.q"), self._act(k, "attn_bwd.k"), self._act(v, "attn_bwd.v"), self._act(do, "attn_bwd.do")
         C = q.shape[1]
         D = C // heads
@@ -626,11 +634,14 @@ class HipOps:
             # K / V map does not in the first-frame branches
             if out is not None:
                 assert out.shape == (rows, C) and out.stride(1) == 1 and out.dtype == self.act_dtype and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0
-                if not covered:
+                if not covered and not accumulate:
                     out.zero_()
                 return out
             return self.empty(rows, C) if covered else torch.zeros((rows, C), dtype=self.act_dtype, device=self.device)
         assert (dk_out is None) == (dv_out is None)
+        if accumulate:
+            assert (dq_out is not None or not need_dq) and (dk_out is not None or not need_dkv), "accumulate adds into dq_out / dk_out / dv_out"
+        flags = 1 if accumulate else 0
         dq = grad_buf(dq_out, q.shape[0], q.shape[0] == groups * q_len) if need_dq else None
         kv_covered = need_dkv and self._kv_map_covers(kmap, groups, q_per_kv, kv_len, k.shape[0])
         dk = grad_buf(dk_out, k.shape[0], kv_covered) if need_dkv else None
@@ -638,7 +649,6 @@ class HipOps:
         assert dk is None or dk.stride(0) == dv.stride(0)
         qm, km, dom = qmap.c(q.stride(0)), kmap.c(k.stride(0)), qmap.c(do.stride(0))
         dqm, dkm = qmap.c(dq.stride(0) if dq is not None else C), kmap.c(dk.stride(0) if dk is not None else C)
-        flags = 0
         if lse is not None:
             assert o is not None and lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == groups * heads * q_len
             o = self._act(o, "attn_bwd.o")
@@ -646,7 +656,7 @@ class HipOps:
             om = qmap.c(o.stride(0))
             rc = self.lib.a3d_attn_delta_bf16(self._stream(), _p(do), _p(o), ctypes.byref(dom), ctypes.byref(om), _p(delta), groups, heads, D, q_len)
             _check(rc, f"a3d_attn_delta_bf16 groups={groups} heads={heads} D={D} q_len={q_len}")
-            flags = 2
+            flags |= 2
         else:
             stats = torch.empty((2, groups * heads * q_len), dtype=torch.float32, device=self.device)
             lse2, delta = stats[0], stats[1]
@@ -667,10 +677,13 @@ class HipOps:
                 run(dq, None, None, dkm, q_per_kv, flags)
             pk = self.empty(groups * kv_len, C)
             pv = self.empty(groups * kv_len, C)
-            run(None, pk, pv, RowMap(1, kv_len, 0, kv_len, 0).c(C), 1, flags | (2 if need_dq else 0))       # (the first call left the statistics in lse2 / delta)
+            # (the first call left the statistics in lse2 / delta; the fresh partials are written, never added to)
+            run(None, pk, pv, RowMap(1, kv_len, 0, kv_len, 0).c(C), 1, (flags & 2) | (2 if need_dq else 0))
             idx = self._shared_kv_rows(kmap, groups, q_per_kv, kv_len)
-            dk.index_copy_(0, idx, pk.view(groups // q_per_kv, q_per_kv, kv_len, C).sum(dim=1).view(-1, C))
-            dv.index_copy_(0, idx, pv.view(groups // q_per_kv, q_per_kv, kv_len, C).sum(dim=1).view(-1, C))
+            put = dk.index_add_ if accumulate else dk.index_copy_
+            put(0, idx, pk.view(groups // q_per_kv, q_per_kv, kv_len, C).sum(dim=1).view(-1, C))
+            put = dv.index_add_ if accumulate else dv.index_copy_
+            put(0, idx, pv.view(groups // q_per_kv, q_per_kv, kv_len, C).sum(dim=1).view(-1, C))
             return dq, dk, dv
         run(dq, dk, dv, dkm, q_per_kv, flags)
         return dq, dk, dv

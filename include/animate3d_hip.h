@@ -248,7 +248,8 @@ int a3d_im2col_in(a3d_stream_t stream, const void* sample, int dtype, void* Y, i
 
 /* Adjoint of a3d_im2col_in: dCol rows [(V F) H W, 64] bf16 (columns k >= 9*C ignored) -> fp32 dX [V, C, F, H, W] =
  * scale * col2im(dCol).  The input gradient of conv_in on the fp32 RGB image of the VAE encoder (4D-SDS,
- * animatemv_guidance.py:365-373); `scale` folds the 2 of imgs * 2 - 1 and the removal of a gradient scale.  9*C <= 64. */
+ * animatemv_guidance.py:365-373); `scale` folds the 2 of imgs * 2 - 1 and the removal of a gradient scale.  9*C <= 64;
+ * dCol 2-byte and dX 4-byte aligned (A3D_EINVAL otherwise). */
 int a3d_im2col_in_bwd(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale);
 
 /* rows [(V F) H W, C] bf16 -> [V, C, F, H, W] in `dtype` (unet_motion_mv_model.py:862). */
@@ -291,7 +292,10 @@ int a3d_cfg_ddim_step_f32(a3d_stream_t stream, const float* eps_pair, const floa
  * video in the first-frame branch; groups % q_per_kv == 0).  dO is the gradient of the attention output scaled by `do_scale`
  * (the forward's out_scale).  lse2 / delta: fp32 scratch [groups * heads * q_len] each (log2-sum-exp and sum_k P dP per query
  * row, recomputed here: the forward keeps nothing).  dQ may be NULL (no query gradient wanted) or dK == dV == NULL (keys / values
- * of frozen text / image tokens); bit 0 of accumulate adds into dQ / dK / dV, bit 1: see a3d_flash_attn_lse below.  head_dim 40 / 64 / 80 / 160. */
+ * of frozen text / image tokens); bit 0 of accumulate adds into dQ / dK / dV, bit 1: see a3d_flash_attn_lse below.  head_dim 40 / 64 / 80 / 160.
+ * Q, K, V, dO, dQ, dK, dV 16-byte aligned (row strides multiples of 8 elements), lse2 / delta 4-byte aligned.  do_scale finite and either
+ * 0 or normal (|do_scale| >= FLT_MIN): 0 gives zero gradients (with bit 0 of accumulate: dQ / dK / dV are left untouched); a subnormal
+ * or non-finite do_scale is A3D_EINVAL. */
 int a3d_flash_attn_bwd_bf16(a3d_stream_t stream, const void* Q, const void* K, const void* V, const void* dO,
                             void* dQ, void* dK, void* dV, float* lse2, float* delta,
                             const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* domap,
@@ -303,8 +307,8 @@ int a3d_flash_attn_bwd_bf16(a3d_stream_t stream, const void* Q, const void* K, c
  * keep the forward's output: a3d_flash_attn_lse is a3d_flash_attn that also returns lse2 [groups][heads][q_len] (log2 of the softmax
  * denominator per query, out of the kernel's own row sums: one float store per query and head; xformers keeps the same tensor for its
  * backward); a3d_attn_delta computes delta[g][h][q] = sum_d dO[q][h, d] * O[q][h, d] (dO rows through `domap`, O rows through `omap`,
- * O = that forward's un-accumulated output).  a3d_flash_attn_bwd with bit 1 of `accumulate` set then reads lse2 / delta instead of
- * recomputing them. */
+ * O = that forward's un-accumulated output; dO / O 16-byte, delta 4-byte aligned).  a3d_flash_attn_bwd with bit 1 of `accumulate` set
+ * then reads lse2 / delta instead of recomputing them. */
 int a3d_flash_attn_lse_bf16(a3d_stream_t stream, const void* Q, const void* K, const void* V, void* O,
                             const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* omap,
                             int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len,
@@ -313,7 +317,8 @@ int a3d_attn_delta_bf16(a3d_stream_t stream, const void* dO, const void* O, cons
                         float* delta, int groups, int heads, int head_dim, int64_t q_len);
 
 /* Temporal attention backward (attention_processor.py:630-636 under autograd): rows ((v*F + f)*L + l); Q / K / V share the row
- * stride ldqkv, dQ / dK / dV share ldd (e.g. the three column ranges of one [rows, 3C] gradient buffer).  frames <= 32. */
+ * stride ldqkv, dQ / dK / dV share ldd (e.g. the three column ranges of one [rows, 3C] gradient buffer).  frames <= 32; all seven
+ * pointers 16-byte aligned, ldqkv / lddo / ldd multiples of 8. */
 int a3d_temporal_attn_bwd_bf16(a3d_stream_t stream, const void* Q, const void* K, const void* V, int64_t ldqkv,
                                const void* dO, int64_t lddo, void* dQ, void* dK, void* dV, int64_t ldd,
                                int videos, int frames, int64_t L, int heads, int head_dim, float scale);
@@ -326,13 +331,14 @@ int a3d_layer_norm_bwd_bf16(a3d_stream_t stream, const void* X, const void* dY, 
 
 /* GroupNorm (+ fused SiLU) backward on channel-last [B][rows][C] (ResnetBlock2D.norm1/2, Transformer2DModel.norm, the 3-D norm of
  * TransformerTemporalModel): stats fp32 [B][groups][2] = (mean, rstd) as a3d_group_norm_apply takes them; ws fp32 [B*C*2] scratch;
- * dgamma / dbeta fp32 [C], ADDED to (both or neither).  C % 8 == 0, C <= 8192, X / dY / dX 16-byte aligned. */
+ * dgamma / dbeta fp32 [C], ADDED to (both or neither).  C % 8 == 0, C <= 8192, X / dY / dX 16-byte aligned, the fp32 operands
+ * 4-byte aligned (A3D_EINVAL otherwise). */
 int a3d_group_norm_bwd_bf16(a3d_stream_t stream, const void* X, const void* dY, const float* gamma, const float* beta,
                             const float* stats, void* dX, float* ws, float* dgamma, float* dbeta,
                             int B, int64_t rows, int C, int groups, int silu);
 
 /* GEGLU backward on the interleaved projection P [M, 2N] of a3d_gemm_geglu (column blocks [32 h | 32 gate]):
- * dP = [dY * gelu(gate) | dY * h * gelu'(gate)] in the same layout.  N % 32 == 0. */
+ * dP = [dY * gelu(gate) | dY * h * gelu'(gate)] in the same layout.  N % 32 == 0; P, dY, dP 16-byte aligned, row strides multiples of 8. */
 int a3d_geglu_bwd_bf16(a3d_stream_t stream, const void* P, int64_t ldp, const void* dY, int64_t lddy, void* dP, int64_t lddp,
                        int64_t M, int64_t N);
 
@@ -354,15 +360,17 @@ int a3d_wgrad_bf16(a3d_stream_t stream, const void* dY, int64_t lddy, const void
  * a 16-byte aligned X reads 16 bytes per lane; any shape otherwise. */
 int a3d_colsum_bf16(a3d_stream_t stream, const void* X, int64_t ldx, int64_t rows, int64_t cols, float* out, float alpha, int accumulate);
 
-/* Y = a X + b Y over n elements (n % 8 == 0): sum of the gradients of two branches. */
+/* Y = a X + b Y over n elements (n % 8 == 0): sum of the gradients of two branches.  X, Y 16-byte aligned. */
 int a3d_axpby_bf16(a3d_stream_t stream, const void* X, void* Y, int64_t n, float a, float b);
 
 /* dgrad helper of the stride-2 down-sampling conv: Z [B, H, W, C] = dY [B, Ho, Wo, C] at the even positions, zero elsewhere
- * (Ho = (H-1)/2 + 1); the input gradient then is a stride-1 a3d_conv3x3 of Z with the flipped, transposed weight. */
+ * (Ho = (H-1)/2 + 1); the input gradient then is a stride-1 a3d_conv3x3 of Z with the flipped, transposed weight.  C % 8 == 0,
+ * dY / Z 16-byte aligned. */
 int a3d_zero_insert2x_bf16(a3d_stream_t stream, const void* dY, void* Z, int B, int H, int W, int C);
 
 /* Backward of the nearest up-sampling in front of the up-sampler conv: dX [B, H, W, C] = sum of the <= 4 positions of
- * dU [B, He, We, C] each input pixel was copied to (He = 2H or 2H-1, likewise We: the forced sizes of unet_motion_mv_model.py:831-837). */
+ * dU [B, He, We, C] each input pixel was copied to (He = 2H or 2H-1, likewise We: the forced sizes of unet_motion_mv_model.py:831-837).
+ * C % 8 == 0, dU / dX 16-byte aligned. */
 int a3d_upsample2x_bwd_bf16(a3d_stream_t stream, const void* dU, void* dX, int B, int H, int W, int He, int We, int C);
 
 /* Optimiser over ONE flat fp32 buffer holding every trainable parameter (and flat gradient / moment buffers of the same length):

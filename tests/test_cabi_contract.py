@@ -1,0 +1,87 @@
+"""CPU checks of the training entry points' preconditions (include/animate3d_hip.h, "Training path"): a pointer that is not aligned to
+the widest access the kernels make through it, or an attention-backward do_scale without a usable reciprocal, is refused with
+A3D_EINVAL before anything reaches the GPU.  The device addresses below are made up and never dereferenced: every call differs from a
+valid launch in exactly one operand, and the argument checks run before the first HIP call, so this runs on a machine without a GPU.
+(No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)"""
+import ctypes
+import math
+
+import pytest
+
+from animate3d_amd.hip_ops import RowMap
+
+A3D_EINVAL = -1
+BASE = 0x7F00_0010_0000          # fake device addresses: BASE + 0x10_0000 * i, 256-byte aligned
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from animate3d_amd import build, hip_ops
+    build.build(verbose=False)
+    return hip_ops.load_library()
+
+
+def _ptrs(names):
+    return {n: BASE + 0x10_0000 * i for i, n in enumerate(names)}
+
+
+def _map(ld):
+    return ctypes.byref(RowMap(1, 64, 0, 64, 0).c(ld))
+
+
+# entry point (bf16 name) -> (operand -> widest access in bytes, argument list of a valid geometry given the operand addresses)
+def _flash_attn_bwd(p, do_scale=1.0, accumulate=0):
+    return [None, p["Q"], p["K"], p["V"], p["dO"], p["dQ"], p["dK"], p["dV"], p["lse2"], p["delta"],
+            _map(960), _map(960), _map(320), _map(960), _map(960), 4, 8, 40, 64, 64, 1, 40 ** -0.5, do_scale, accumulate]
+
+
+CASES = {
+    "a3d_flash_attn_bwd_bf16": (dict(Q=16, K=16, V=16, dO=16, dQ=16, dK=16, dV=16, lse2=4, delta=4), _flash_attn_bwd),
+    "a3d_attn_delta_bf16": (dict(dO=16, O=16, delta=4),
+                            lambda p: [None, p["dO"], p["O"], _map(320), _map(320), p["delta"], 4, 8, 40, 64]),
+    "a3d_temporal_attn_bwd_bf16": (dict(Q=16, K=16, V=16, dO=16, dQ=16, dK=16, dV=16),
+                                   lambda p: [None, p["Q"], p["K"], p["V"], 960, p["dO"], 320, p["dQ"], p["dK"], p["dV"], 960,
+                                              2, 16, 9, 8, 40, 40 ** -0.5]),
+    "a3d_group_norm_bwd_bf16": (dict(X=16, dY=16, gamma=4, beta=4, stats=4, dX=16, ws=4, dgamma=4, dbeta=4),
+                                lambda p: [None, p["X"], p["dY"], p["gamma"], p["beta"], p["stats"], p["dX"], p["ws"], p["dgamma"], p["dbeta"],
+                                           2, 64, 320, 32, 1]),
+    "a3d_geglu_bwd_bf16": (dict(P=16, dY=16, dP=16), lambda p: [None, p["P"], 2560, p["dY"], 1280, p["dP"], 2560, 70, 1280]),
+    "a3d_axpby_bf16": (dict(X=16, Y=16), lambda p: [None, p["X"], p["Y"], 1024, 0.5, 2.0]),
+    "a3d_zero_insert2x_bf16": (dict(dY=16, Z=16), lambda p: [None, p["dY"], p["Z"], 2, 6, 6, 64]),
+    "a3d_upsample2x_bwd_bf16": (dict(dU=16, dX=16), lambda p: [None, p["dU"], p["dX"], 2, 3, 5, 6, 10, 64]),
+    "a3d_im2col_in_bwd": (dict(dCol=2, dX=4), lambda p: [None, p["dCol"], p["dX"], 2, 3, 2, 8, 8, 1.0]),
+    "a3d_wgrad_bf16": (dict(dY=16, X=16, ws=16),
+                       lambda p: [None, p["dY"], 320, p["X"], 320, p["dW"], 320, p["ws"], 64, 320, 320, 1.0, 0]),
+    "a3d_softmax_rows_bwd_bf16": (dict(P=8, dP=16, dS=8), lambda p: [None, p["P"], 512, p["dP"], 512, p["dS"], 512, 16, 512, 1.0]),
+}
+
+
+def _twin(name, f16):
+    if not f16:
+        return name
+    return name[:-5] + "_f16" if name.endswith("_bf16") else name + "_f16"
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("entry", sorted(CASES))
+def test_misaligned_operand_is_refused(lib, entry, f16):
+    """One call per operand, that operand moved off its alignment by the largest offset that still keeps the element size (8 bytes for
+    a 16-byte access, 2 for a 4-byte one, 1 for a 2-byte one): a column view at a 4-element offset is the case this guards."""
+    align, args_of = CASES[entry]
+    fn = getattr(lib, _twin(entry, f16))
+    names = list(align) + [n for n in ("dW",) if entry == "a3d_wgrad_bf16"]
+    for operand, a in align.items():
+        p = _ptrs(names)
+        p[operand] += a // 2
+        rc = fn(*args_of(p))
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +{a // 2} bytes returned {rc}"
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("do_scale", [1e-40, -1e-45, 1.0e-38 / 2, math.inf, -math.inf, math.nan])
+def test_flash_attn_bwd_refuses_do_scale_without_reciprocal(lib, do_scale, f16):
+    """dP starts at -delta / do_scale: a subnormal do_scale (whose reciprocal overflows or loses range) or a non-finite one is refused
+    rather than turned into NaN gradients.  (0 and every normal value are accepted: GPU tier, tests/test_train_kernels_gpu.py.)"""
+    fn = getattr(lib, _twin("a3d_flash_attn_bwd_bf16", f16))
+    for accumulate in (0, 1, 3):
+        assert fn(*_flash_attn_bwd(_ptrs(CASES["a3d_flash_attn_bwd_bf16"][0]), do_scale, accumulate)) == A3D_EINVAL

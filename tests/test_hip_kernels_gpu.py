@@ -791,3 +791,71 @@ def test_group_norm_two_source(ops, ref, B, rows, Ca, Cb, silu):
     got = ops.group_norm2(xa, xb, B, rows, gamma, beta, 32, 1e-5, silu)
     check(f"group_norm2 B{B} rows{rows} {Ca}+{Cb} silu={silu}", got, ref.group_norm(cat, B, rows, gamma, beta, 32, 1e-5, silu))
     assert torch.equal(got, want)
+
+
+# ------------------------------------------------------------------ the split-K workspace under graph capture and across streams
+def _conv_inputs(B, H, W, Cin, Cout, seed):
+    return rnd(B * H * W, Cin, seed=seed), rnd(Cout, 9 * Cin, seed=seed + 1, scale=(9 * Cin) ** -0.5)
+
+
+def _planned(ops, shape):
+    return max((v for k, v in ops._ws_plan.items() if k[0] == "conv" and k[1:6] == tuple(shape)), default=0)
+
+
+def test_split_k_workspace_outlives_a_graph_capture():
+    """A captured split-K conv keeps its workspace pointer for every replay.  After the capture an eager call of a larger split shape
+    grows the op set's workspace; the block it replaces must not be what the replay writes its fp32 partials into, or the replay
+    corrupts whatever tensor the caching allocator handed that block to next."""
+    from animate3d_amd.hip_ops import HipOps
+    ops = HipOps()                                     # fresh: its workspace is sized by this test alone
+    S1 = (32, 8, 8, 2560, 1280)
+    x1, w1 = _conv_inputs(*S1, seed=301)
+    eager = ops.conv3x3(x1, *S1[:3], w1, None)[0].clone()
+    need1 = _planned(ops, S1)
+    assert need1 > 0, "S1 was expected to split"
+    old_bytes = max(need1, 1 << 20)                    # the workspace that call allocated (HipOps._workspace rounds up to 1 MiB)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        y = ops.conv3x3(x1, *S1[:3], w1, None)[0]
+    # eager calls of larger split shapes: at least one plans a strictly larger workspace, so the eager buffer is regrown
+    # (the plan fills the chip, so it does not grow with the shape by itself: level-1 / 2 convolutions of a 64 x 64 latent, 12 videos)
+    larger = [(12, 16, 16, 2560, 1280), (12, 32, 32, 1920, 640), (12, 32, 32, 1280, 640), (12, 16, 16, 1280, 1280), (12, 32, 32, 640, 640)]
+    for i, S2 in enumerate(larger):
+        x2, w2 = _conv_inputs(*S2, seed=311 + 2 * i)
+        ops.conv3x3(x2, *S2[:3], w2, None)
+    grown = max(_planned(ops, S2) for S2 in larger)
+    assert grown > old_bytes, (grown, old_bytes)
+    torch.cuda.synchronize()
+    sentinel = 0x5A
+    fillers = [torch.full((old_bytes,), sentinel, dtype=torch.uint8, device="cuda") for _ in range(8)]
+    graph.replay()
+    torch.cuda.synchronize()
+    for i, f in enumerate(fillers):
+        assert bool((f == sentinel).all()), f"filler {i} (the size of the replaced workspace) was overwritten by the graph replay"
+    assert torch.equal(y, eager), "replayed split-K conv differs from the eager result"
+
+
+def test_split_k_convs_on_two_streams():
+    """Split-K convs issued on two side streams without any ordering between them: each stream's partials have a workspace of their
+    own, so every result is bit-equal to the same call on one stream."""
+    from animate3d_amd.hip_ops import HipOps
+    ops = HipOps()
+    S = (32, 8, 8, 2560, 1280)
+    xs = [_conv_inputs(*S, seed=401 + 2 * i) for i in range(4)]
+    want = [ops.conv3x3(x, *S[:3], w, None)[0] for x, w in xs]
+    assert _planned(ops, S) > 0, "the shape was expected to split"
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    assert sa.cuda_stream != sb.cuda_stream
+    cur = torch.cuda.current_stream()
+    sa.wait_stream(cur)
+    sb.wait_stream(cur)
+    got = []
+    for rep in range(3):
+        for i, (x, w) in enumerate(xs):
+            with torch.cuda.stream(sa if i % 2 == 0 else sb):
+                got.append((i, ops.conv3x3(x, *S[:3], w, None)[0]))
+    cur.wait_stream(sa)
+    cur.wait_stream(sb)
+    torch.cuda.synchronize()
+    for i, y in got:
+        assert torch.equal(y, want[i]), f"conv {i} on a side stream differs from the single-stream result"

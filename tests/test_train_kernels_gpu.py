@@ -388,3 +388,201 @@ def test_autograd_ops_attention_and_norm_compositions(ops, ref):
     want = _grads(lambda x, g, bt: r.group_norm(x, V, F * L, g, bt, 32, 1e-6, False), [gx.float(), gamma, beta], dy)
     for name, g, wnt in zip(("dx", "dgamma", "dbeta"), got, want):
         check(f"autograd 3-D group_norm {name}", g, wnt, tol)
+
+
+# ------------------------------------------------------------------ attention backward at the edge values of do_scale
+def _bits(t):
+    return t.view(torch.int16)
+
+
+def _attn_cases(C, n, F, L, dt):
+    """The multi-view and first-frame self-attention shapes above: (name, q, k, v, do, qmap, kmap, groups, q_len, kv_len, q_per_kv)."""
+    b = 2
+    rows = b * n * F * L
+    kvq = rnd(rows, 3 * C, seed=1, dtype=dt)
+    q, k, v = kvq[:, 2 * C:], kvq[:, :C], kvq[:, C:2 * C]
+    do = rnd(rows, C, seed=2, dtype=dt)
+    qm = RowMap(gdiv=F, ga=n * F * L, gb=L, seg_len=L, seg_stride=F * L)
+    k0 = RowMap(gdiv=F, ga=n * F * L, gb=0, seg_len=L, seg_stride=F * L)
+    return [("multi-view", q, k, v, do, qm, qm, b * F, n * L, n * L, 1), ("first-frame", q, k, v, do, qm, k0, b * F, n * L, n * L, F)]
+
+
+def _cross_case(C, T, L, dt):
+    V, F = 2, 3
+    q, do = rnd(V * F * L, C, seed=1, dtype=dt), rnd(V * F * L, C, seed=2, dtype=dt)
+    kv = rnd(V * T, 2 * C, seed=3, dtype=dt)
+    return ("cross", q, kv[:, :C], kv[:, C:], do, RowMap(1, L, 0, L, 0), RowMap(F, T, 0, T, 0), V * F, L, T, F)
+
+
+SELF_SHAPES = [(320, 2, 2, 96), (640, 2, 3, 40), (1280, 3, 2, 16)]          # head_dim 40 / 80 / 160, ragged tails
+CROSS_SHAPES = [(320, 77, 50), (640, 16, 50), (1280, 77, 50)]
+
+
+def _do_scale_cases(ops, shape, kind):
+    dt = ops.act_dtype
+    return _attn_cases(*shape, dt) if kind == "self" else [_cross_case(*shape, dt)]
+
+
+def _stats(ops, case, heads, out_scale, with_stats):
+    """{} (the recomputing path) or the o= / lse= of a forward run with out_scale = do_scale (a3d_flash_attn_lse + a3d_attn_delta)."""
+    _, q, k, v, _, qm, km, G, S, T, _ = case
+    if not with_stats:
+        return {}
+    o, lse = ops.flash_attn(q, k, v, qm, km, G, heads, S, T, out_scale=out_scale, with_lse=True)
+    return dict(o=o, lse=lse)
+
+
+@pytest.mark.parametrize("with_stats", [False, True], ids=["recompute", "forward-stats"])
+@pytest.mark.parametrize("kind,shape", [("self", s) for s in SELF_SHAPES] + [("cross", s) for s in CROSS_SHAPES])
+def test_flash_attn_bwd_do_scale_zero(ops, kind, shape, with_stats):
+    """do_scale = 0 (an IP-Adapter branch with ip_scale 0: the forward's out_scale is 0, so delta is 0 too): the gradients are exactly
+    zero — not -0 * inf = NaN from a dP seeded with -delta / do_scale — and, added into caller buffers, leave them bit for bit as they
+    were.  (No relative-L2 check here: the reference norm is 0.)"""
+    heads = 8
+    for case in _do_scale_cases(ops, shape, kind):
+        name, q, k, v, do, qm, km, G, S, T, share = case
+        kw = _stats(ops, case, heads, 0.0, with_stats)
+        for need_dkv in ((True, False) if kind == "cross" else (True,)):
+            got = ops.flash_attn_bwd(q, k, v, do, qm, km, G, heads, S, T, q_per_kv=share, do_scale=0.0, need_dkv=need_dkv, **kw)
+            for g, t in zip(got, "qkv"):
+                if g is None:
+                    continue
+                assert torch.isfinite(g.float()).all(), f"{name} d{t}: non-finite gradient at do_scale 0"
+                assert float(g.float().abs().max()) == 0.0, f"{name} d{t}: nonzero gradient at do_scale 0"
+            # accumulate into pre-filled [rows, C] column views of wider buffers (the fused-projection gradient)
+            C = q.shape[1]
+            wq, wkv = rnd(q.shape[0], 2 * C, seed=7, dtype=ops.act_dtype), rnd(k.shape[0], 3 * C, seed=8, dtype=ops.act_dtype)
+            before = (wq.clone(), wkv.clone())
+            outs = dict(dq_out=wq[:, C:])
+            if need_dkv:
+                outs.update(dk_out=wkv[:, :C], dv_out=wkv[:, 2 * C:])
+            ops.flash_attn_bwd(q, k, v, do, qm, km, G, heads, S, T, q_per_kv=share, do_scale=0.0, need_dkv=need_dkv, accumulate=True, **outs, **kw)
+            torch.cuda.synchronize()
+            assert torch.equal(_bits(wq), _bits(before[0])), f"{name}: accumulated dQ buffer changed at do_scale 0"
+            assert torch.equal(_bits(wkv), _bits(before[1])), f"{name}: accumulated dK / dV buffer changed at do_scale 0"
+
+
+@pytest.mark.parametrize("with_stats", [False, True], ids=["recompute", "forward-stats"])
+@pytest.mark.parametrize("kind,shape", [("self", s) for s in SELF_SHAPES] + [("cross", s) for s in CROSS_SHAPES])
+def test_flash_attn_bwd_do_scale_edge_values(ops, ref, kind, shape, with_stats):
+    """A negative do_scale, a small power of two and (bf16: fp16 cannot hold 1e-30-sized gradients) 1e-30, whose reciprocal 1e30
+    seeds dP: against the fp32 reference.  The gradients are linear in do_scale; at 1e-30 both sides are compared divided by it in
+    fp64 (an fp32 norm of 1e-31-sized values underflows), the reference taken at do_scale 1."""
+    dt, heads = ops.act_dtype, 8
+    scales = [-0.6, 2.0 ** -10] + ([1e-30] if dt == torch.bfloat16 else [])
+    for case in _do_scale_cases(ops, shape, kind):
+        name, q, k, v, do, qm, km, G, S, T, share = case
+        for s in scales:
+            kw = _stats(ops, case, heads, s, with_stats)
+            got = ops.flash_attn_bwd(q, k, v, do, qm, km, G, heads, S, T, q_per_kv=share, do_scale=s, **kw)
+            tiny = abs(s) < 1e-20
+            want = ref.flash_attn_bwd(q, k, v, do, qm, km, G, heads, S, T, do_scale=1.0 if tiny else s)
+            for g, w, t in zip(got, want, "qkv"):
+                if tiny:
+                    g = g.double() / s
+                check(f"flash_attn_bwd {name} do_scale={s:g} d{t} D={q.shape[1] // heads}", g, w, ATTN_TOL[dt])
+
+
+def test_autograd_ops_ip_adapter_with_zero_scale(ops, ref):
+    """The IP-Adapter accumulation of test_autograd_ops_attention_and_norm_compositions with ip_scale = 0 (out_scale 0.0): the image
+    branch contributes nothing, and the shared query projection's gradient is finite and matches the reference."""
+    from animate3d_amd.autograd_ops import AutogradOps
+    dt = ops.act_dtype
+    a, r = AutogradOps(ops), AutogradOps(ref)
+    C, heads, n, F, L, T, nt = 320, 8, 2, 2, 32, 77, 4
+    V = n
+    rows = V * F * L
+    qc = RowMap(gdiv=1, ga=L, gb=0, seg_len=L, seg_stride=0)
+
+    def cross(o, proj, kvt, kvi):          # Q of both branches: one column block of a fused projection output
+        q2 = o.split_cols(proj, 0, C, 2 * C)[0]
+        ca = o.flash_attn(q2, kvt[:, :C], kvt[:, C:], qc, RowMap(F, T, 0, T, 0), V * F, heads, L, T, accumulation_target=True)
+        o.flash_attn(q2, kvi[:, :C], kvi[:, C:], qc, RowMap(F, nt, 0, nt, 0), V * F, heads, L, nt, out=ca, out_scale=0.0, accumulate=True)
+        return ca
+
+    proj, kvt, kvi = rnd(rows, 2 * C, seed=3, dtype=dt), rnd(V * T, 2 * C, seed=4, dtype=dt), rnd(V * nt, 2 * C, seed=5, dtype=dt)
+    dy = rnd(rows, C, seed=6)
+    got = _grads(lambda p: cross(a, p, kvt, kvi), [proj], dy)
+    want = _grads(lambda p: cross(r, p, kvt.float(), kvi.float()), [proj.float()], dy)
+    assert torch.isfinite(got[0].float()).all(), "IP-Adapter branch at scale 0 made the projection gradient non-finite"
+    check("autograd text + IP (scale 0) cross-attention d(proj)", got[0], want[0], ATTN_TOL[dt])
+
+
+# ------------------------------------------------------------------ alignment contract of the training entry points
+# A [rows, C] view at a 4-element (8-byte) column offset has a row stride that is a multiple of 8 and passes every shape check; the
+# kernels behind these entry points read and write it 16 bytes at a time.  Their C-ABI refuses such a pointer before launching
+# (tests/test_cabi_contract.py proves that on the CPU, so nothing here launches on a misaligned pointer), and HipOps raises.
+def _col_view(rows, C, seed, dt):
+    return rnd(rows, C + 8, seed=seed, dtype=dt)[:, 4:4 + C]
+
+
+def _flat_view(rows, C, seed, dt):
+    """Contiguous [rows, C] at an 8-byte offset into its storage: passes every is_contiguous() guard."""
+    return rnd(rows * C + 8, seed=seed, dtype=dt)[4:4 + rows * C].view(rows, C)
+
+
+def _refused(fn):
+    with pytest.raises(RuntimeError, match="A3D_EINVAL"):
+        fn()
+    torch.cuda.synchronize()
+
+
+def test_training_entry_points_refuse_8_byte_offset_views(ops):
+    dt, heads = ops.act_dtype, 8
+    # attention backward: each 16-bit input in turn (dq_out / dk_out / dv_out are asserted 16-byte aligned in HipOps itself)
+    C, n, F, L = 320, 2, 2, 64
+    rows = 2 * n * F * L
+    qm = RowMap(gdiv=F, ga=n * F * L, gb=L, seg_len=L, seg_stride=F * L)
+    wide = [rnd(rows, C + 8, seed=i, dtype=dt) for i in range(4)]           # (K and V must share a row stride)
+    good = [w[:, 8:8 + C] for w in wide]
+    for i in range(4):
+        args = list(good)
+        args[i] = wide[i][:, 4:4 + C]
+        _refused(lambda: ops.flash_attn_bwd(*args, qm, qm, 2 * F, heads, n * L, n * L))
+    o, lse = ops.flash_attn(*good[:3], qm, qm, 2 * F, heads, n * L, n * L, with_lse=True)
+    _refused(lambda: ops.flash_attn_bwd(*good, qm, qm, 2 * F, heads, n * L, n * L, o=_col_view(rows, C, 20, dt), lse=lse))   # a3d_attn_delta
+    # temporal attention backward
+    videos, F, L = 2, 16, 9
+    r = videos * F * L
+    qkv = rnd(r, 3 * C, seed=21, dtype=dt)
+    do = rnd(r, C, seed=22, dtype=dt)
+    qkv_off = _col_view(r, 3 * C, 23, dt)                                    # Q, K and V share one row stride
+    _refused(lambda: ops.temporal_attn_bwd(qkv_off[:, :C], qkv_off[:, C:2 * C], qkv_off[:, 2 * C:], do, videos, F, L, heads))
+    _refused(lambda: ops.temporal_attn_bwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], _col_view(r, C, 24, dt), videos, F, L, heads))
+    # GroupNorm backward (contiguous tensors at an 8-byte offset)
+    B, rws = 2, 64
+    x, dy = rnd(B * rws, C, seed=25, dtype=dt), rnd(B * rws, C, seed=26, dtype=dt)
+    gamma, beta = 1.0 + 0.2 * rnd(C, seed=27), 0.1 * rnd(C, seed=28)
+    stats = ops.group_norm_stats(x, B, rws, 32, 1e-5)
+    _refused(lambda: ops.group_norm_bwd(_flat_view(B * rws, C, 29, dt), dy, B, rws, gamma, beta, 32, stats, True))
+    _refused(lambda: ops.group_norm_bwd(x, _flat_view(B * rws, C, 30, dt), B, rws, gamma, beta, 32, stats, True))
+    # GEGLU backward, axpby, the conv helpers
+    p, dy = rnd(70, 2560, seed=31, dtype=dt), rnd(70, 1280, seed=32, dtype=dt)
+    _refused(lambda: ops.geglu_bwd(_col_view(70, 2560, 33, dt), dy))
+    _refused(lambda: ops.geglu_bwd(p, _col_view(70, 1280, 34, dt)))
+    y = rnd(100, 320, seed=35, dtype=dt)
+    _refused(lambda: ops.axpby_(_flat_view(100, 320, 36, dt), y, 0.5, 2.0))
+    _refused(lambda: ops.axpby_(y.clone(), _flat_view(100, 320, 37, dt), 0.5, 2.0))
+    _refused(lambda: ops.zero_insert2x(_flat_view(2 * 3 * 3, 64, 38, dt), 2, 6, 6))
+    _refused(lambda: ops.upsample2x_bwd(_flat_view(2 * 6 * 10, 64, 39, dt), 2, 3, 5, 6, 10))
+    # weight gradient (checked since it was written)
+    _refused(lambda: ops.wgrad(_col_view(300, 320, 40, dt), rnd(300, 320, seed=41, dtype=dt)))
+
+
+def test_narrow_access_entry_points_take_8_byte_offset_views_bit_exactly(ops):
+    """The entry points whose kernels access at most 8 bytes at a time accept the same views and return what the aligned copy gives."""
+    dt = ops.act_dtype
+    # im2col_in_bwd: 2-byte reads of dCol
+    V, C, F, H, W = 2, 3, 2, 8, 8
+    dcol = _flat_view(V * F * H * W, 64, 51, dt)
+    assert dcol.data_ptr() % 16 == 8
+    got, want = ops.im2col_in_bwd(dcol, V, C, F, H, W, 2.0), ops.im2col_in_bwd(dcol.clone(), V, C, F, H, W, 2.0)
+    assert torch.equal(got, want)
+    # softmax_rows_bwd: 8-byte reads of P, 8-byte stores of dS
+    M, N = 64, 512
+    pv = torch.softmax(rnd(M, N + 8, seed=52), dim=1).to(dt)[:, 4:4 + N]
+    dp = rnd(M, N, seed=53)
+    out = torch.empty(M, N + 8, dtype=dt, device="cuda")[:, 4:4 + N]
+    got = ops.softmax_rows_bwd(pv, dp, 0.5, out=out)
+    want = ops.softmax_rows_bwd(pv.contiguous(), dp, 0.5)
+    assert torch.equal(got, want)

@@ -312,6 +312,38 @@ def test_forward_is_hip_graph_capturable(models):
         assert torch.equal(y_static, y_eager), "graph replay differs from the eager forward"
 
 
+def test_graph_replay_after_the_split_k_workspace_grew(models):
+    """A captured forward bakes the split-K workspace pointer into the graph (split-K is on for every conv with B*Ho*Wo <= 32768: the mid
+    block, the whole 4D-SDS shape).  An eager forward of the same model at a larger latent afterwards grows the op set's workspace; the
+    replay must still write into memory that belongs to it, not into the freed block.  Runs on a fresh op set, so the growth is this
+    test's own."""
+    from animate3d_amd.hip_ops import HipOps
+    ocfg, ref, hip, _ = models
+    saved = hip._ops
+    hip._ops = ops = HipOps(hip.device, torch.bfloat16)
+    try:
+        # 32x32 latent (the 4D-SDS one): the mid block and levels 1 - 3 split; the 16x16 latent of the other tests splits nothing
+        inp_a = _cuda(O.synthetic_inputs(ocfg, 2, N_VIEWS, FRAMES, (32, 32), seed=31))
+        inp_b = _cuda(O.synthetic_inputs(ocfg, 2, N_VIEWS, FRAMES, (32, 32), seed=32))
+        step = hip.capture_graph(**inp_a)
+        captured = max(ops._ws_plan.values(), default=0)
+        assert captured > 0, "the captured forward was expected to use split-K"
+        hip(**_cuda(O.synthetic_inputs(ocfg, 2 * N_VIEWS, N_VIEWS, FRAMES, (64, 64), seed=33, cfg_doubled=True)))
+        assert max(ops._ws_plan.values()) > max(captured, 1 << 20), "the larger forward was expected to grow the workspace"
+        torch.cuda.synchronize()
+        # blocks of the replaced workspace's size, as the caching allocator hands out freed memory to the next tensors
+        fillers = [torch.full((max(captured, 1 << 20),), 0x5A, dtype=torch.uint8, device="cuda") for _ in range(4)]
+        y_static = step(**inp_b).sample.clone()
+        torch.cuda.synchronize()
+        for i, f in enumerate(fillers):
+            assert bool((f == 0x5A).all()), f"filler {i} (the size of the replaced workspace) was overwritten by the graph replay"
+        del fillers
+        y_eager = hip(**inp_b).sample
+        assert torch.equal(y_static, y_eager), "graph replay after the workspace grew differs from the eager forward"
+    finally:
+        hip._ops = saved
+
+
 def test_graph_capture_with_a_cu_reservation_active(models):
     """The CU reservation of the sharded path (parallel.py: compute-units left free for an overlapped RCCL collective) is a
     per-call argument of the C-ABI (``flags`` of a3d_gemm / a3d_conv3x3, include/animate3d_hip.h), held per op set — not process
