@@ -114,6 +114,15 @@ _SIGNATURES = {
     "a3d_sqnorm_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int]),
     "a3d_clip_ctrl_f32": (c_int, [c_vp, c_vp, c_f32, c_f32, c_vp]),
     "a3d_adamw_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp]),
+    # Gaussian splat rasterizer (include/animate3d_hip.h, csrc/splat.hip): fp32 only, no storage twins
+    "a3d_gs_preprocess_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gs_duplicate_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gs_tile_ranges_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64]),
+    "a3d_gs_render_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gs_render_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp]),
+    "a3d_gs_preprocess_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gs_sum_batch_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64]),
 }
 # fp16-storage twins (include/animate3d_hip.h, last section): same signatures
 _UNSUFFIXED_TWINS = ("a3d_im2col_in", "a3d_unpack_out", "a3d_im2col_in_bwd")      # boundary kernels: the bf16 build has no suffix

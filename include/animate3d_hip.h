@@ -383,6 +383,45 @@ int a3d_clip_ctrl_f32(a3d_stream_t stream, const float* sqnorm, float max_norm, 
 int a3d_adamw_f32(a3d_stream_t stream, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* ctrl);
 
+/* Differentiable Gaussian splat rasterizer (csrc/splat.hip; contract in animate3d_amd/splat.py), fp32, B cameras per launch.
+ * Per-Gaussian inputs are [*, N, k] contiguous; their *_bs argument is the element stride between images (0: one tensor shared
+ * by all images).  Exactly one of shs ([*, N, M, 3], degree deg <= 3) / colors ([*, N, 3]) is non-NULL.  view / proj [B, 4, 4]
+ * row-vector convention, campos [B, 3], tanfovx / tanfovy [B].  Per-(image, Gaussian) buffers are [B, N, ...]:
+ *   a3d_gs_preprocess_f32      radii, xy [B, N, 2] (pixels), depth, conic_o [B, N, 4] (conic, opacity), rgb [B, N, 3], clamped (SH clamp bits),
+ *                              tiles_touched
+ *   a3d_gs_duplicate_f32       offsets = inclusive prefix sum of tiles_touched (int64); writes one key / value per touched tile:
+ *                              key = (image * tiles + tile) << 32 | float bits of depth, value = Gaussian index
+ *   a3d_gs_tile_ranges_f32     ranges [B * tiles, 2] = [start, end) of each (image, tile) in the L sorted keys (zeroed first)
+ *   a3d_gs_render_f32          perm = the stable sort's permutation (sorted -> duplicated position, int64); image [B, 3, H, W], depth / alpha /
+ *                              T_final [B, H, W], n_contrib [B, H, W]
+ *   a3d_gs_render_bwd_f32      d_depth / d_alpha may be NULL (zero); rows [L, 12]: per instance, in duplicated order, the gradient w.r.t.
+ *                              centre (2), conic (3), opacity, colour (3), depth, summed over the tile's pixels
+ *   a3d_gs_preprocess_bwd_f32  per (image, Gaussian) input gradients [B, N, ...] (d_means2d: NDC centre, third component 0)
+ *   a3d_gs_sum_batch_f32       dst[k] = sum over b of src[b * M + k], b in order */
+int a3d_gs_preprocess_f32(a3d_stream_t stream, int B, int N, const float* means, int64_t means_bs, const float* scales, int64_t scales_bs,
+                          const float* rots, int64_t rots_bs, const float* opac, int64_t opac_bs, const float* shs, int64_t shs_bs, int M,
+                          int deg, const float* colors, int64_t colors_bs, const float* view, const float* proj, const float* campos,
+                          const float* tanfovx, const float* tanfovy, int H, int W, float scale_mod, int* radii, float* xy, float* depth,
+                          float* conic_o, float* rgb, int* clamped, int* tiles_touched);
+int a3d_gs_duplicate_f32(a3d_stream_t stream, int B, int N, int H, int W, const float* xy, const float* depth, const int* radii,
+                         const int64_t* offsets, int64_t* keys, int* vals);
+int a3d_gs_tile_ranges_f32(a3d_stream_t stream, const int64_t* keys, int64_t L, int* ranges, int64_t n_tiles);
+int a3d_gs_render_f32(a3d_stream_t stream, int B, int N, int H, int W, const int* ranges, const int64_t* perm, const int* vals,
+                      const float* xy, const float* conic_o, const float* rgb, const float* depth, const float* bg,
+                      float* out_img, float* out_depth, float* out_alpha, float* T_final, int* n_contrib);
+int a3d_gs_render_bwd_f32(a3d_stream_t stream, int B, int N, int H, int W, const int* ranges, const int64_t* perm, const int* vals,
+                          const float* xy, const float* conic_o, const float* rgb, const float* depth, const float* bg,
+                          const float* T_final, const int* n_contrib, const float* d_img, const float* d_depth,
+                          const float* d_alpha, float* rows);
+int a3d_gs_preprocess_bwd_f32(a3d_stream_t stream, int B, int N, const float* means, int64_t means_bs, const float* scales, int64_t scales_bs,
+                              const float* rots, int64_t rots_bs, const float* opac, int64_t opac_bs, const float* shs, int64_t shs_bs, int M,
+                              int deg, const float* colors, int64_t colors_bs, const float* view, const float* proj, const float* campos,
+                              const float* tanfovx, const float* tanfovy, int H, int W, float scale_mod, const int* radii,
+                              const int* clamped, const int64_t* offsets, const int* tiles_touched, const float* rows,
+                              float* d_means2d, float* d_means, float* d_scales, float* d_rots, float* d_opac, float* d_shs,
+                              float* d_colors);
+int a3d_gs_sum_batch_f32(a3d_stream_t stream, const float* src, float* dst, int B, int64_t M);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
  * IEEE fp16 as the storage type (same signature, same semantics, same fp32 accumulation / statistics / softmax; the MFMA is
