@@ -422,6 +422,38 @@ int a3d_gs_preprocess_bwd_f32(a3d_stream_t stream, int B, int N, const float* me
                               float* d_colors);
 int a3d_gs_sum_batch_f32(a3d_stream_t stream, const float* src, float* dst, int B, int64_t M);
 
+/* 4-D Gaussian deformation field: two-scale HexPlane grid + five 32-wide MLPs (csrc/deform4d.hip; contract in animate3d_amd/deform4d.py),
+ * fp32, every frame of a step per call.  Replaces Gaussian4DModel.interpolate_ms_features / get_xyz / get_rotation / get_scaling
+ * (custom/threestudio-animate3d/geometry/gaussian_4d.py:450-548) and their per-image loop (diff_gaussian_rasterizer_advanced_4d.py:77-135).
+ * xyz [N, 3], scaling [N, 3], rotation [N, 4], timestamps [T].  grid: the twelve planes repacked texel-major ([H][W][16] each) in one
+ * buffer; plane_desc is a HOST array [36] = float offset (multiple of 16) | W | H of plane k = 6 scale + pair, pairs in
+ * itertools.combinations(range(4), 2) order, W the resolution of the pair's first coordinate (every resolution >= 2).
+ * weights [5, 1152]: per network layers.0.weight [32, 32] then layers.2.weight zero-padded to [4, 32]; networks delta_xyz, delta_rot,
+ * delta_scaling, global_rot, global_trans.  flags: 1 use_global_trans, 2 deform_scales, 4 first_frame_trainable.
+ * img_start [T + 1] / img_list [B]: the images that show each frame, ascending (int32).
+ *   a3d_dg_cells_f32           cells [12, N] int32: per plane the cell of each Gaussian (row-major (H - 1) x (W - 1) for a spatial plane,
+ *                              the cell along the spatial axis for a time plane); the caller stable-sorts them into the plan
+ *   a3d_dg_mean_partials       blocks per frame of the mean's first reduction stage (size of mpart)
+ *   a3d_dg_forward_f32         sp [N, 32] (product of the spatial planes), mpart [T, partials, 32], gmean [T, 32], glob [T, 12] (R | trans)
+ *                              (the last three only with use_global_trans); means / scales [B, N, 3], rots [B, N, 4]
+ *   a3d_dg_backward_ws_floats  floats of the backward's workspace
+ *   a3d_dg_backward_f32        order [12, N] / starts: the plan (per plane the Gaussians sorted by cell and each cell's first position,
+ *                              cells + 1 entries per plane, planes back to back); d_means / d_scales / d_rots [B, N, ...];
+ *                              d_grid in the packing of grid, d_weights [5, 1152], d_scaling [N, 3], d_rotation [N, 4].  No atomics:
+ *                              every sum runs in a fixed order (images of a frame ascending, Gaussians in plan order, frames ascending) */
+int a3d_dg_cells_f32(a3d_stream_t stream, int N, const float* xyz, const int64_t* plane_desc, int* cells);
+int64_t a3d_dg_mean_partials(int N);
+int a3d_dg_forward_f32(a3d_stream_t stream, int T, int N, int B, const float* xyz, const float* scaling, const float* rotation,
+                       const float* timestamps, const float* grid, const int64_t* plane_desc, const float* weights, int flags,
+                       const int* img_start, const int* img_list, float* sp, float* mpart, float* gmean, float* glob, float* means,
+                       float* scales, float* rots);
+int64_t a3d_dg_backward_ws_floats(int T, int N, const int64_t* plane_desc);
+int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, const float* xyz, const float* scaling, const float* rotation,
+                        const float* timestamps, const float* grid, const int64_t* plane_desc, const float* weights, int flags,
+                        const int* img_start, const int* img_list, const float* sp, const float* gmean, const float* glob,
+                        const int* order, const int* starts, const float* d_means, const float* d_scales, const float* d_rots,
+                        float* ws, float* d_grid, float* d_weights, float* d_scaling, float* d_rotation);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
  * IEEE fp16 as the storage type (same signature, same semantics, same fp32 accumulation / statistics / softmax; the MFMA is

@@ -1,0 +1,206 @@
+"""Dense torch restatement of the deformation-field contract of animate3d_amd/deform4d.py (the oracle of the deform4d tests), written
+for clarity: plain ``F.grid_sample`` and ``F.linear``, one frame at a time, dtype-generic (float64 and float32).  Also the seeded scene
+generator of those tests, with the two input conditions the comparison needs (see ``make_scene``)."""
+import itertools
+import math
+
+import torch
+import torch.nn.functional as F
+
+PAIRS = list(itertools.combinations(range(4), 2))
+LOCAL = ("delta_xyz_network", "delta_rot_network", "delta_scaling_network")
+GLOBAL = ("global_rot_network", "global_trans_network")
+OUT = {"delta_xyz_network": 3, "delta_rot_network": 4, "delta_scaling_network": 3, "global_rot_network": 3, "global_trans_network": 3}
+
+
+RELEASED = ((50, 50, 50, 8), (100, 100, 100, 16))
+# every scene a deform4d test compares on: (N, grid_size, timestamps, seed); built with use_global_trans on and off
+SCENES = {
+    "gpu_parity": (4000, RELEASED, (0.35, -1.0, -0.62, 1.0, 0.05), 21),
+    "golden": (64, ((6, 5, 7, 3), (12, 10, 14, 6)), (-1.0, -0.4, 0.3, 1.0), 0),
+    "gradcheck": (5, ((3, 4, 5, 2), (4, 3, 6, 3)), (-1.0, -0.2, 0.7), 3),
+}
+
+
+def named_scene(name, use_global_trans=True):
+    N, grid_size, ts, seed = SCENES[name]
+    return make_scene(N, grid_size, ts, seed, use_global_trans=use_global_trans)
+
+
+def cell_ids(xyz: torch.Tensor, grid_size) -> torch.Tensor:
+    """Torch restatement of a3d_dg_cells_f32 (any device): [12, N] cell of each Gaussian per plane k = 6 s + p."""
+    out = []
+    for (W, H), (a, b) in zip([(int(r[a]), int(r[b])) for r in grid_size for a, b in PAIRS], PAIRS * len(grid_size)):
+        def cell(u, R):
+            x = ((u.float() + 1) * 0.5 * (R - 1)).clamp(0, R - 1)
+            return x.floor().long().clamp(max=R - 2)
+        cx = cell(xyz[:, a], W)
+        out.append(cx if b == 3 else cell(xyz[:, b], H) * (W - 1) + cx)
+    return torch.stack(out).to(torch.int32)
+
+
+def sample_plane(plane, coords):
+    """plane [1, C, H, W], coords [N, 2] (first coordinate along W) -> [N, C]"""
+    out = F.grid_sample(plane, coords.view(1, 1, -1, 2), align_corners=True, mode="bilinear", padding_mode="border")
+    return out.view(plane.shape[1], -1).t()
+
+
+def hidden_features(pts, grids):
+    feats = []
+    for planes in grids:
+        prod = 1.0
+        for plane, pair in zip(planes, PAIRS):
+            prod = prod * sample_plane(plane, pts[:, list(pair)])
+        feats.append(prod)
+    return torch.cat(feats, dim=-1)
+
+
+def mlp(weights, x, diag=None, name=None):
+    pre = F.linear(x, weights[0])
+    if diag is not None:
+        diag.setdefault("pre", {}).setdefault(name, []).append(pre.detach())
+    return F.linear(torch.relu(pre), weights[1])
+
+
+def build_rotation(q):
+    q = q / q.norm(dim=1, keepdim=True)
+    r, x, y, z = q.unbind(1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                        2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                        2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).view(-1, 3, 3)
+
+
+def extract_rotation(A, diag=None):
+    """Matrix -> quaternion (r, x, y, z) with the contract's four-way branch; normalised."""
+    a = lambda i, j: A[:, i, j]
+    tr = a(0, 0) + a(1, 1) + a(2, 2)
+    c1 = tr > 0
+    c2 = ~c1 & (a(0, 0) > a(1, 1)) & (a(0, 0) > a(2, 2))
+    c3 = ~c1 & ~c2 & (a(1, 1) > a(2, 2))
+    branch = torch.where(c1, 0, torch.where(c2, 1, torch.where(c3, 2, 3)))
+    if diag is not None:
+        diag.setdefault("branch", []).append(branch)
+        diag.setdefault("margins", []).append(torch.stack([tr, a(0, 0) - a(1, 1), a(0, 0) - a(2, 2), a(1, 1) - a(2, 2)], 1).detach())
+    one = torch.ones_like(tr)
+    safe = lambda v, m: torch.where(m, v, one)              # keep sqrt away from the branches that do not use it
+    t0 = torch.sqrt(safe(tr + 1, branch == 0)) * 2
+    t1 = torch.sqrt(safe(1 + a(0, 0) - a(1, 1) - a(2, 2), branch == 1)) * 2
+    t2 = torch.sqrt(safe(1 + a(1, 1) - a(0, 0) - a(2, 2), branch == 2)) * 2
+    t3 = torch.sqrt(safe(1 + a(2, 2) - a(0, 0) - a(1, 1), branch == 3)) * 2
+    q0 = torch.stack([0.25 * t0, (a(2, 1) - a(1, 2)) / t0, (a(0, 2) - a(2, 0)) / t0, (a(1, 0) - a(0, 1)) / t0], 1)
+    q1 = torch.stack([(a(2, 1) - a(1, 2)) / t1, 0.25 * t1, (a(0, 1) + a(1, 0)) / t1, (a(0, 2) + a(2, 0)) / t1], 1)
+    q2 = torch.stack([(a(0, 2) - a(2, 0)) / t2, (a(0, 1) + a(1, 0)) / t2, 0.25 * t2, (a(1, 2) + a(2, 1)) / t2], 1)
+    q3 = torch.stack([(a(1, 0) - a(0, 1)) / t3, (a(0, 2) + a(2, 0)) / t3, (a(1, 2) + a(2, 1)) / t3, 0.25 * t3], 1)
+    b = branch[:, None]
+    q = torch.where(b == 0, q0, torch.where(b == 1, q1, torch.where(b == 2, q2, q3)))
+    return q / q.norm(dim=1, keepdim=True)
+
+
+def euler_matrix(angles):
+    roll, pitch, yaw = angles.unbind(0)
+    zero, one = torch.zeros_like(roll), torch.ones_like(roll)
+    rx = torch.stack([one, zero, zero, zero, roll.cos(), -roll.sin(), zero, roll.sin(), roll.cos()]).view(3, 3)
+    ry = torch.stack([pitch.cos(), zero, pitch.sin(), zero, one, zero, -pitch.sin(), zero, pitch.cos()]).view(3, 3)
+    rz = torch.stack([yaw.cos(), -yaw.sin(), zero, yaw.sin(), yaw.cos(), zero, zero, zero, one]).view(3, 3)
+    return rz @ (ry @ rx)
+
+
+def deform_frame(xyz, scaling, rotation, t, grids, nets, use_global_trans, deform_scales, bypass, diag=None):
+    if bypass:
+        return xyz, torch.exp(scaling), F.normalize(rotation, dim=1)
+    pts = torch.cat([xyz, torch.ones_like(xyz[:, :1]) * t], dim=1)
+    hidden = hidden_features(pts, grids)
+    pos, rot = xyz, rotation
+    if use_global_trans:
+        g = hidden.mean(0, keepdim=True)
+        angles = torch.sigmoid(mlp(nets["global_rot_network"], g, diag, "global_rot_network")) * 2 * math.pi - math.pi
+        trans = torch.sigmoid(mlp(nets["global_trans_network"], g, diag, "global_trans_network")) * 2 - 1
+        R = euler_matrix(angles[0])
+        pos = (R @ xyz.t()).t() + trans
+        rot = extract_rotation(R @ build_rotation(rotation), diag)
+    means = pos + mlp(nets["delta_xyz_network"], hidden, diag, "delta_xyz_network")
+    rots = F.normalize(rot + mlp(nets["delta_rot_network"], hidden, diag, "delta_rot_network"), dim=1)
+    if deform_scales:
+        scales = torch.exp(scaling + mlp(nets["delta_scaling_network"], hidden, diag, "delta_scaling_network"))
+    else:
+        scales = torch.exp(scaling)
+    return means, scales, rots
+
+
+def deform(xyz, scaling, rotation, timestamps, grids, nets, image_to_time=None, use_global_trans=False, deform_scales=True,
+           first_frame_trainable=False, diag=None):
+    """-> means [B, N, 3], scales [B, N, 3], rotations [B, N, 4]; ``diag`` (a dict) collects pre-activations and branch data per frame."""
+    frames = []
+    for f in range(timestamps.shape[0]):
+        bypass = (not first_frame_trainable) and float(timestamps[f]) == -1.0
+        frames.append(deform_frame(xyz, scaling, rotation, timestamps[f], grids, nets, use_global_trans, deform_scales, bypass, diag))
+    idx = range(len(frames)) if image_to_time is None else [int(i) for i in image_to_time]
+    return tuple(torch.stack([frames[i][k] for i in idx]) for k in range(3))
+
+
+def cast(scene, dtype, device="cpu"):
+    """The tensors of a scene in another dtype / on another device (fresh leaves)."""
+    c = lambda t: t.detach().to(device=device, dtype=dtype).clone()
+    return dict(xyz=c(scene["xyz"]), scaling=c(scene["scaling"]), rotation=c(scene["rotation"]), timestamps=c(scene["timestamps"]),
+                grids=[[c(p) for p in g] for g in scene["grids"]], nets={k: (c(a), c(b)) for k, (a, b) in scene["nets"].items()})
+
+
+def _unsafe(scene, use_global_trans, relu_margin=1e-5, branch_margin=1e-3):
+    """Per-Gaussian mask of inputs that sit within rounding of a ReLU switch or of a quaternion branch threshold (float64 evaluation)."""
+    s = cast(scene, torch.float64)
+    diag = {}
+    deform(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], s["nets"], use_global_trans=use_global_trans,
+           first_frame_trainable=True, diag=diag)
+    N = s["xyz"].shape[0]
+    bad = torch.zeros(N, dtype=torch.bool)
+    global_bad = False
+    for name, pres in diag["pre"].items():
+        for pre in pres:
+            near = pre.abs() < relu_margin * pre.pow(2).mean().sqrt()
+            if pre.shape[0] == 1:
+                global_bad |= bool(near.any())
+            else:
+                bad |= near.any(1)
+    for m in diag.get("margins", []):
+        bad |= (m.abs() < branch_margin).any(1)
+    return bad, global_bad
+
+
+def make_scene(N, grid_size, timestamps, seed, use_global_trans=True, spread=0.7):
+    """Seeded inputs and parameters (float32, CPU).  Gaussians are resampled, not masked, until none has, in any frame and network, a
+    hidden pre-activation below 1e-5 of that layer's RMS (a ReLU unit within fp32 rounding of zero switches a whole gradient term), nor a
+    trace / diagonal difference of R build_rotation(q) within 1e-3 of a branch threshold of the quaternion extraction (whose sign flips
+    between branches).  ``spread`` > 0.5 puts some points outside [-1, 1]: the border clamp."""
+    g = torch.Generator().manual_seed(seed)
+    grids = []
+    for reso in grid_size:
+        planes = []
+        for a, b in PAIRS:
+            lo, hi = (0.7, 1.3) if b == 3 else (0.4, 1.4)
+            planes.append(torch.rand(1, 16, reso[b], reso[a], generator=g) * (hi - lo) + lo)
+        grids.append(planes)
+    names = LOCAL + GLOBAL
+    nets = {n: (torch.randn(32, 32, generator=g) * 0.4, torch.randn(OUT[n], 32, generator=g) * 0.15) for n in names}
+    scene = dict(xyz=torch.randn(N, 3, generator=g) * spread, scaling=torch.rand(N, 3, generator=g) * 2 - 4,
+                 rotation=torch.randn(N, 4, generator=g), timestamps=torch.as_tensor(timestamps, dtype=torch.float32), grids=grids, nets=nets)
+    for _ in range(50):
+        bad, global_bad = _unsafe(scene, use_global_trans)
+        assert not global_bad, "a global-network pre-activation sits at zero: pick another seed"
+        k = int(bad.sum())
+        if k == 0:
+            scene["resampled"] = _
+            return scene
+        scene["xyz"][bad] = torch.randn(k, 3, generator=g) * spread
+        scene["rotation"][bad] = torch.randn(k, 4, generator=g)
+    raise AssertionError("resampling did not converge")
+
+
+def patterns(scene, dtype, use_global_trans):
+    """(ReLU on/off pattern per network, quaternion branches) of every frame in ``dtype``."""
+    s = cast(scene, dtype)
+    diag = {}
+    deform(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], s["nets"], use_global_trans=use_global_trans,
+           first_frame_trainable=True, diag=diag)
+    relu = {k: torch.stack([p > 0 for p in v]) for k, v in diag["pre"].items()}
+    branch = torch.stack(diag["branch"]) if "branch" in diag else None
+    return relu, branch

@@ -1,0 +1,237 @@
+"""The deformation-field kernels (csrc/deform4d.hip) against the float64 restatement tests/deform_ref.py, their bitwise guarantees, and
+the config-5 SDS step starting from the field's parameters.
+
+Tolerance: per compared tensor, e32 = relative L2 of the float32 CPU restatement against the float64 one on the same inputs; the kernels'
+relative L2 against float64 must be at most max(4 e32, 16 * 2^-24).  The factor 4 covers what legitimately differs from torch's fp32 (the
+order of the N-term mean and of the T N-term weight-gradient sums, FMA contraction, device exp / sin / cos); the floor, sixteen fp32
+roundings, is for tensors whose e32 lands at one or two roundings.  Scenes come from deform_ref.make_scene, which resamples Gaussians
+that sit at a ReLU switch or a quaternion branch threshold, so no element is left out of any comparison."""
+import math
+
+import pytest
+import torch
+
+from animate3d_amd import deform4d, splat
+from tests import deform_ref, gs_ref
+
+pytestmark = pytest.mark.gpu
+
+RELEASED = deform_ref.RELEASED
+FLOOR = 16 * 2.0 ** -24
+
+
+def _rel(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
+
+
+def _leaves(s, names):
+    out = {"scaling": s["scaling"], "rotation": s["rotation"]}
+    for si, g in enumerate(s["grids"]):
+        for pi, p in enumerate(g):
+            out[f"grids.{si}.{pi}"] = p
+    for n in names:
+        out[f"{n}.layers.0.weight"], out[f"{n}.layers.2.weight"] = s["nets"][n]
+    return out
+
+
+def _run_ref(scene, dtype, names, i2t, cots, **kw):
+    s = deform_ref.cast(scene, dtype)
+    leaves = _leaves(s, names)
+    for t in leaves.values():
+        t.requires_grad_(True)
+    outs = deform_ref.deform(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], {n: s["nets"][n] for n in names},
+                             image_to_time=i2t, **kw)
+    loss = sum((o * c.to(dtype)).sum() for o, c in zip(outs, cots))
+    grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
+    grads = {k: (torch.zeros_like(t) if g is None else g) for (k, t), g in zip(leaves.items(), grads)}
+    return dict(zip(("means", "scales", "rotations"), outs)), grads
+
+
+def _run_hip(scene, names, i2t, cots, **kw):
+    s = deform_ref.cast(scene, torch.float32, "cuda")
+    leaves = _leaves(s, names)
+    for t in leaves.values():
+        t.requires_grad_(True)
+    outs = deform4d.deform_gaussians(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], {n: s["nets"][n] for n in names},
+                                     image_to_time=None if i2t is None else i2t.cuda(), **kw)
+    loss = sum((o * c.cuda()).sum() for o, c in zip(outs, cots))
+    grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
+    grads = {k: (torch.zeros_like(t) if g is None else g) for (k, t), g in zip(leaves.items(), grads)}
+    return dict(zip(("means", "scales", "rotations"), outs)), grads
+
+
+@pytest.mark.parametrize("use_global", [False, True])
+@pytest.mark.parametrize("deform_scales", [False, True])
+@pytest.mark.parametrize("fft", [False, True])
+def test_forward_and_gradients_against_float64(use_global, deform_scales, fft):
+    scene = deform_ref.named_scene("gpu_parity", use_global)         # tests/test_deform4d_host.py checks the same scene on the CPU
+    N = scene["xyz"].shape[0]
+    r32, b32 = deform_ref.patterns(scene, torch.float32, use_global)
+    r64, b64 = deform_ref.patterns(scene, torch.float64, use_global)
+    assert all(torch.equal(r32[k], r64[k]) for k in r64) and (b64 is None or torch.equal(b32, b64))     # e32 below measures rounding only
+    names = deform_ref.LOCAL + (deform_ref.GLOBAL if use_global else ())
+    i2t = torch.tensor([3, 0, 4, 1, 1, 2, 0, 3])                                   # repeated and unordered frames
+    g = torch.Generator().manual_seed(4)
+    cots = [torch.randn(len(i2t), N, k, generator=g) for k in (3, 3, 4)]
+    kw = dict(use_global_trans=use_global, deform_scales=deform_scales, first_frame_trainable=fft)
+    o64, g64 = _run_ref(scene, torch.float64, names, i2t, cots, **kw)
+    o32, g32 = _run_ref(scene, torch.float32, names, i2t, cots, **kw)
+    oh, gh = _run_hip(scene, names, i2t, cots, **kw)
+    torch.cuda.synchronize()
+    failures = []
+    for kind, r64, r32, got in (("out", o64, o32, oh), ("grad", g64, g32, gh)):
+        for k in r64:
+            if float(r64[k].detach().abs().max()) == 0.0:                 # no path to this tensor in this configuration: exactly zero
+                print(f"[deform4d g{int(use_global)} s{int(deform_scales)} f{int(fft)}] {kind} {k}: reference is zero")
+                assert float(got[k].detach().abs().max()) == 0.0, k
+                continue
+            e32, err = _rel(r32[k], r64[k]), _rel(got[k], r64[k])
+            bar = max(4 * e32, FLOOR)
+            print(f"[deform4d g{int(use_global)} s{int(deform_scales)} f{int(fft)}] {kind} {k}: e32 {e32:.3e} kernel {err:.3e} bar {bar:.3e}")
+            if not err <= bar:
+                failures.append((kind, k, e32, err, bar))
+    assert not failures, failures
+
+
+def test_cells_kernel_matches_definition():
+    """a3d_dg_cells_f32 (what the plan is sorted from) against the torch restatement of the cell assignment, border points included."""
+    g = torch.Generator().manual_seed(9)
+    xyz = torch.randn(20000, 3, generator=g) * 0.7
+    xyz[:3] = torch.tensor([[1.0, -1.0, 0.0], [-1.0, 1.0, 1.0], [3.0, -3.0, 0.5]])
+    plan = deform4d.BinningPlan(xyz.cuda(), RELEASED)
+    want = deform_ref.cell_ids(xyz, RELEASED)
+    assert torch.equal(plan.cells.cpu(), want)                 # (u + 1) / 2 is exact either way it is contracted, so the floors agree
+    order, starts = deform4d.build_plan(plan.cells, deform4d.plane_cells(RELEASED))
+    assert torch.equal(order, plan.order) and torch.equal(starts, plan.starts)
+
+
+def _module(use_global, seed=0, grid_size=RELEASED):
+    torch.manual_seed(seed)
+    m = deform4d.HexPlaneDeformation(grid_size=grid_size, use_global_trans=use_global).cuda()
+    with torch.no_grad():
+        for p in m.parameters():
+            if p.dim() == 4:
+                p.uniform_(0.5, 1.3)
+            elif float(p.abs().max()) == 0.0:
+                p.normal_(0.0, 0.15)
+    return m
+
+
+def _inputs(N, seed):
+    g = torch.Generator().manual_seed(seed)
+    return ((torch.randn(N, 3, generator=g) * 0.6).cuda(), (torch.rand(N, 3, generator=g) * 2 - 4).cuda().requires_grad_(True),
+            torch.randn(N, 4, generator=g).cuda().requires_grad_(True))
+
+
+def _grads(m, xyz, sc, ro, ts, i2t, cots, **kw):
+    outs = m(xyz, sc, ro, ts, i2t, **kw)
+    leaves = [sc, ro] + list(m.parameters())
+    return outs, torch.autograd.grad(sum((o * c).sum() for o, c in zip(outs, cots)), leaves)
+
+
+def test_backward_is_bitwise_reproducible_and_independent_of_image_grouping():
+    N, T, V = 6000, 16, 4
+    m = _module(True)
+    xyz, sc, ro = _inputs(N, 1)
+    ts = torch.linspace(-1, 1, T).cuda()
+    i2t = (torch.arange(V * T) % T).cuda()                                          # (n f) image order
+    g = torch.Generator().manual_seed(2)
+    cots = [torch.randn(V * T, N, k, generator=g).cuda() for k in (3, 3, 4)]
+    o1, g1 = _grads(m, xyz, sc, ro, ts, i2t, cots)
+    o2, g2 = _grads(m, xyz, sc, ro, ts, i2t, cots)
+    assert all(torch.equal(a, b) for a, b in zip(g1, g2)) and all(torch.equal(a, b) for a, b in zip(o1, o2))
+    pre = []
+    for c in cots:                                                                  # each frame's views summed in ascending image order
+        c = c.view(V, T, N, -1)
+        pre.append(((c[0] + c[1]) + c[2]) + c[3])
+    o3, g3 = _grads(m, xyz, sc, ro, ts, None, pre)
+    names = ["scaling", "rotation"] + [k for k, _ in m.named_parameters()]
+    for k, a, b in zip(names, g1, g3):
+        assert torch.equal(a, b), k
+    for a, b in zip(o1, o3):
+        assert torch.equal(a.view(V, T, N, -1)[2], b)
+    perm = torch.randperm(T, generator=g).cuda()
+    o4 = m(xyz, sc, ro, ts[perm])
+    for a, b in zip(o3, o4):
+        assert torch.equal(a[perm], b)
+
+
+def test_xyz_gradient_refused_and_plan_follows_in_place_changes():
+    N = 3000
+    m = _module(False)
+    xyz, sc, ro = _inputs(N, 3)
+    ts = torch.tensor([-0.5, 0.2, 0.9]).cuda()
+    with pytest.raises(NotImplementedError):
+        m(xyz.clone().requires_grad_(True), sc, ro, ts)
+    g = torch.Generator().manual_seed(5)
+    cots = [torch.randn(3, N, k, generator=g).cuda() for k in (3, 3, 4)]
+    o1, _ = _grads(m, xyz, sc, ro, ts, None, cots)
+    plan1 = m._plan
+    _grads(m, xyz, sc, ro, ts, None, cots)
+    assert m._plan is plan1                                                         # cached while xyz is untouched
+    xyz.mul_(-1.0).add_(0.05)
+    o2, g2 = _grads(m, xyz, sc, ro, ts, None, cots)
+    assert m._plan is not plan1 and not torch.equal(o1[0], o2[0])
+    fresh = _module(False)
+    fresh.load_state_dict(m.state_dict())
+    o3, g3 = _grads(fresh, xyz.clone(), sc, ro, ts, None, cots)
+    assert all(torch.equal(a, b) for a, b in zip(o2, o3)) and all(torch.equal(a, b) for a, b in zip(g2, g3))
+
+
+def test_sds_config5_step_from_deformation_field_gpu():
+    """BASELINE config 5 one link earlier than test_sds_config5_step_from_gaussians_gpu: HexPlaneDeformation -> rasterize_gaussians ->
+    sds_guidance_loss -> loss.backward() fills every plane and every MLP weight; one Adam step on them changes the rendered image."""
+    from animate3d_amd.config import UNetConfig
+    from animate3d_amd.sds import sds_guidance_loss
+    from animate3d_amd.unet import MVUNetMotionModel
+    from animate3d_amd.vae import AutoencoderKLEncoder
+    from oracle import vae_ref as R
+    n, f, H, W, N, dt = 4, 16, 256, 256, 20000, torch.float16
+    enc = AutoencoderKLEncoder(device="cuda")
+    enc.load_state_dict(R.init_synthetic_weights(R.VAEEncoderRef(), seed=1).state_dict(), strict=True)
+    enc = enc.to(dt).eval()
+    unet = MVUNetMotionModel(UNetConfig(), num_views=n, device="cuda")
+    unet.init_synthetic(seed=0)
+    unet = unet.to(dt).eval()
+    g = torch.Generator().manual_seed(12)
+    xyz = (torch.randn(N, 3, generator=g) * 0.6).cuda()
+    scaling = (torch.rand(N, 3, generator=g) * 2.0 - 4.2).cuda()
+    rotation = torch.randn(N, 4, generator=g).cuda()
+    opac = (torch.sigmoid(torch.randn(N, 1, generator=g) * 1.5) * 0.1).cuda()
+    shs = (torch.randn(N, 16, 3, generator=g) * 0.3).cuda()
+    field = deform4d.HexPlaneDeformation(use_global_trans=True).cuda()
+    with torch.no_grad():                                       # the reference's zero last layers give zero gradient to everything before them
+        for name, p in field.named_parameters():
+            if name.endswith("layers.2.weight"):
+                p.normal_(0.0, 0.02, generator=None)
+    c2w_v = torch.stack([gs_ref.look_at((3.5 * math.cos(a), 3.5 * math.sin(a), 0.0)) for a in (0.0, math.pi / 2, math.pi, 1.5 * math.pi)])
+    c2w = c2w_v[:, None].expand(n, f, 4, 4).reshape(n * f, 4, 4).cuda()
+    fovy = torch.full((n * f,), math.radians(40.0), device="cuda")
+    w2c, full, center = splat.get_cam_info_gaussian(c2w, fovy, fovy, 0.1, 100.0)
+    ts = torch.linspace(-1, 1, f).cuda()
+    i2t = (torch.arange(n * f) % f).cuda()
+
+    def render():
+        means, scales, rots = field(xyz, scaling, rotation, ts, i2t)
+        img, _, _, _ = splat.rasterize_gaussians(means, scales, rots, opac, shs=shs, viewmatrix=w2c, projmatrix=full, campos=center,
+                                                 tanfovx=torch.tan(fovy / 2), tanfovy=torch.tan(fovy / 2), image_height=H, image_width=W,
+                                                 bg=torch.ones(3, device="cuda"), sh_degree=3)
+        return img
+    img = render()
+    text = torch.randn(2 * n, 77, 768, generator=g).cuda()
+    emb = torch.randn(n, 1024, generator=g).cuda()
+    vae_noise = torch.randn(n * f, 4, 32, 32, generator=g).cuda()
+    loss, _ = sds_guidance_loss(enc, unet, img.permute(0, 2, 3, 1), torch.tensor([500], device="cuda"), text, emb, c2w, n_view=n, n_frame=f,
+                                weights_dtype=dt, vae_noise=vae_noise, generator=torch.Generator(device="cuda").manual_seed(2))
+    opt = torch.optim.Adam(field.parameters(), lr=1e-2)
+    loss.backward()
+    torch.cuda.synchronize()
+    assert torch.isfinite(loss)
+    for name, p in field.named_parameters():
+        assert p.grad is not None and torch.isfinite(p.grad).all() and float(p.grad.abs().max()) > 0.0, name
+        print(f"[sds config 5 from the deformation field] {name}: |grad| max {p.grad.abs().max().item():.3e}")
+    opt.step()
+    with torch.no_grad():
+        img2 = render()
+    assert float((img2 - img.detach()).abs().max()) > 0.0
