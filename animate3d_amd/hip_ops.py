@@ -131,6 +131,10 @@ _SIGNATURES = {
     "a3d_dg_backward_ws_floats": (c_i64, [c_int, c_int, c_vp]),
     "a3d_dg_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # ARAP rigidity loss and its k-NN graph (csrc/arap.hip): fp32 only, no storage twins
+    "a3d_knn_f32": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_f32, c_vp, c_vp]),
+    "a3d_arap_energy_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_arap_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 # fp16-storage twins (include/animate3d_hip.h, last section): same signatures
 _UNSUFFIXED_TWINS = ("a3d_im2col_in", "a3d_unpack_out", "a3d_im2col_in_bwd")      # boundary kernels: the bf16 build has no suffix

@@ -15,6 +15,9 @@
  *   - ld* = leading dimension (elements between consecutive rows)
  *   - every function returns 0 on success, a negative A3D_E* code on bad arguments, or a
  *     positive hipError_t from the launch.  Nothing here allocates or synchronises.
+ *   - the Gaussian side of the 4D-SDS stage (splat rasterizer, deformation field, ARAP rigidity loss and its k-NN graph) is fp32
+ *     at the interface, with no storage twins; the ARAP entry points keep their rotations and per-sample energies in fp64
+ *     buffers that the caller allocates
  */
 #ifndef ANIMATE3D_HIP_H
 #define ANIMATE3D_HIP_H
@@ -453,6 +456,28 @@ int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, const float* x
                         const int* img_start, const int* img_list, const float* sp, const float* gmean, const float* glob,
                         const int* order, const int* starts, const float* d_means, const float* d_scales, const float* d_rots,
                         float* ws, float* d_grid, float* d_weights, float* d_scaling, float* d_rotation);
+
+/* ARAP rigidity loss on the Gaussian trajectories and its k-NN graph (csrc/arap.hip; contract in animate3d_amd/arap.py), fp32 at the
+ * interface.  Replaces cal_connectivity_from_points / estimate_rotation / cal_arap_error (custom/threestudio-animate3d/systems/util.py:58-215)
+ * and the pytorch3d.ops.knn_points they are built on.
+ *   a3d_knn_f32            exact K nearest other points of each of N points [N, 3] by dx*dx + dy*dy + dz*dz, ascending by (distance,
+ *                          index); 1 <= K <= 16 (else A3D_EUNSUPPORTED), N > K.  Columns >= least_edge_num whose distance is not below
+ *                          radius2 become index -1, distance +inf (least_edge_num >= K: no cut).  nn_idx [N, K] int32, nn_dist [N, K]
+ *   a3d_arap_energy_f32    source [Nv, 3]; targets: F frames of [Nv, 3], frame f at targets + f * targets_bs floats; nn_idx [Nv, K] (-1: no
+ *                          edge); weight [Nv, K] or NULL (1 on edges); sample_idx [S] int32.  rot [F, S, 9] fp64 (kept for the backward),
+ *                          rot_f32 [F, S, 9] or NULL, energy [F * S] fp64 workspace, loss [1]: the sum over frames, samples and edges in a
+ *                          fixed order
+ *   a3d_arap_backward_f32  order [S (K + 1)] / starts [Nv + 1]: the (sample, slot) pairs s (K + 1) + c (slot 0: the sample's vertex, slot k + 1
+ *                          its k-th neighbour) stable-sorted by vertex, absent ones last, and each vertex's first position; grad_out [1]
+ *                          or NULL (zero); d_targets [F, Nv, 3] contiguous, d_source [Nv, 3] or NULL.  The rotations are constants.  No
+ *                          atomics: each vertex sums its entries in list order, frames ascending; rows without entries are written 0 */
+int a3d_knn_f32(a3d_stream_t stream, int N, const float* points, int K, int least_edge_num, float radius2, int* nn_idx, float* nn_dist);
+int a3d_arap_energy_f32(a3d_stream_t stream, int F, int Nv, int K, int S, const float* source, const float* targets, int64_t targets_bs,
+                        const int* nn_idx, const float* weight, const int* sample_idx, double* rot, float* rot_f32, double* energy,
+                        float* loss);
+int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, int S, const float* source, const float* targets, int64_t targets_bs,
+                          const int* nn_idx, const float* weight, const int* sample_idx, const double* rot, const int* order,
+                          const int* starts, const float* grad_out, float* d_targets, float* d_source);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
