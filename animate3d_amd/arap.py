@@ -45,24 +45,14 @@ length depends on the data: it synchronises, once per graph.)
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional, Tuple
 
 import torch
 
-from .hip_ops import _check, _p, load_library
+from .f32_stage import TensorKeyed, gather_plan, launch, require_f32_cuda, require_index_cuda
+from .hip_ops import _p
 
 K_MAX = 16
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _require_f32_cuda(name: str, t: torch.Tensor):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-        raise RuntimeError(f"{name}: expected a float32 CUDA tensor, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')} "
-                           "(no CPU fallback)")
 
 
 def _check_k(K: int, Nv: int):
@@ -78,23 +68,21 @@ def knn_graph(points: torch.Tensor, K: int, radius: Optional[float] = None, leas
         raise ValueError(f"points: expected [Nv, 3], got {tuple(points.shape)}")
     Nv, K = points.shape[0], int(K)
     _check_k(K, Nv)
-    _require_f32_cuda("points", points)
+    require_f32_cuda("points", points)
     if least_edge_num < 0:
         raise ValueError("least_edge_num must not be negative")
-    lib = load_library()
     x = points.detach().contiguous()
     nn_idx = torch.empty(Nv, K, dtype=torch.int32, device=points.device)
     nn_dist = torch.empty(Nv, K, dtype=torch.float32, device=points.device)
     least, r2 = (K, float("inf")) if radius is None else (int(least_edge_num), float(radius) ** 2)
-    with torch.cuda.device(points.device):
-        _check(lib.a3d_knn_f32(_stream(), Nv, _p(x), K, least, r2, _p(nn_idx), _p(nn_dist)), "a3d_knn_f32")
+    launch("a3d_knn_f32", points.device, Nv, _p(x), K, least, r2, _p(nn_idx), _p(nn_dist))
     return nn_idx, nn_dist
 
 
-class ArapGraph:
-    """The k-NN graph of one ``xyz``: ``nn_idx`` / ``nn_dist`` of ``knn_graph``.  It is keyed exactly as ``deform4d.BinningPlan`` is: a weak
-    reference to the tensor, its data pointer, ``_version``, shape and device, plus K, radius and ``least_edge_num``; an in-place change of
-    ``xyz`` therefore invalidates it.  ``refresh(xyz)`` searches again only then, so the search runs once per stage, not once per step."""
+class ArapGraph(TensorKeyed):
+    """The k-NN graph of one ``xyz``: ``nn_idx`` / ``nn_dist`` of ``knn_graph``.  It is a ``f32_stage.TensorKeyed``, as ``deform4d.BinningPlan``
+    is, with K, radius and ``least_edge_num`` in the key; an in-place change of ``xyz`` therefore invalidates it.  ``refresh(xyz)`` searches
+    again only then, so the search runs once per stage, not once per step."""
 
     def __init__(self, xyz: torch.Tensor, K: int = 3, radius: Optional[float] = None, least_edge_num: int = 3, *, neighbours=None):
         self.K, self.radius, self.least_edge_num = int(K), None if radius is None else float(radius), int(least_edge_num)
@@ -105,8 +93,7 @@ class ArapGraph:
         if neighbours is None:
             neighbours = knn_graph(xyz, self.K, self.radius, self.least_edge_num)
         self.nn_idx, self.nn_dist = neighbours
-        self.key = self._key(xyz, self.K, self.radius, self.least_edge_num)
-        self._xyz = weakref.ref(xyz)                             # the address alone could be a later tensor on the same allocator block
+        self.bind(xyz, self.K, self.radius, self.least_edge_num)
         self.builds += 1
 
     @classmethod
@@ -115,13 +102,8 @@ class ArapGraph:
         """A graph that was found elsewhere (a mesh's connectivity: a dense ``nn_idx`` with -1 entries), under the same key."""
         return cls(xyz, nn_idx.shape[1], radius, least_edge_num, neighbours=(nn_idx, nn_dist))
 
-    @staticmethod
-    def _key(xyz, K, radius, least_edge_num):
-        return (xyz.data_ptr(), xyz._version, tuple(xyz.shape), str(xyz.device), int(K), None if radius is None else float(radius),
-                int(least_edge_num))
-
     def matches(self, xyz: torch.Tensor) -> bool:
-        return self._xyz() is xyz and self.key == self._key(xyz, self.K, self.radius, self.least_edge_num)
+        return super().matches(xyz, self.K, self.radius, self.least_edge_num)
 
     def refresh(self, xyz: torch.Tensor) -> "ArapGraph":
         if not self.matches(xyz):
@@ -139,23 +121,21 @@ def inverse_list(sample_idx: torch.Tensor, nn_idx: torch.Tensor) -> Tuple[torch.
     nbr = nn_idx.long()[v.clamp(0, Nv - 1)]
     ids = torch.cat([v[:, None], nbr], dim=1)
     ids = torch.where(ok[:, None] & (ids >= 0) & (ids < Nv), ids, torch.full_like(ids, Nv)).reshape(-1)
-    srt, order = torch.sort(ids, stable=True)
-    starts = torch.searchsorted(srt, torch.arange(Nv + 1, device=ids.device))
-    return order.to(torch.int32).contiguous(), starts.to(torch.int32).contiguous()
+    return gather_plan(ids, Nv)
 
 
 class _ArapEnergy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, source, targets, nn_idx, weight, sample_idx, want_rot):
-        lib, dev = load_library(), source.device
+        dev = source.device
         F, Nv, K, S = targets.shape[0], source.shape[0], nn_idx.shape[1], sample_idx.shape[0]
         src, tgt = source.detach(), targets.detach()
         rot = torch.empty(F, S, 9, dtype=torch.float64, device=dev)
         rot32 = torch.empty(F, S, 3, 3, dtype=torch.float32, device=dev) if want_rot else None
         energy = torch.empty(F * S, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        _check(lib.a3d_arap_energy_f32(_stream(), F, Nv, K, S, _p(src), _p(tgt), tgt.stride(0), _p(nn_idx), _p(weight), _p(sample_idx),
-                                       _p(rot), _p(rot32), _p(energy), _p(loss)), "a3d_arap_energy_f32")
+        launch("a3d_arap_energy_f32", dev, F, Nv, K, S, _p(src), _p(tgt), tgt.stride(0), _p(nn_idx), _p(weight), _p(sample_idx), _p(rot),
+               _p(rot32), _p(energy), _p(loss))
         ctx.save_for_backward(src, tgt, nn_idx, weight, sample_idx, rot)
         ctx.need_src = ctx.needs_input_grad[0]
         if want_rot:
@@ -166,14 +146,14 @@ class _ArapEnergy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_loss, _d_rot):
         src, tgt, nn_idx, weight, sample_idx, rot = ctx.saved_tensors
-        lib, dev = load_library(), src.device
+        dev = src.device
         F, Nv, K, S = tgt.shape[0], src.shape[0], nn_idx.shape[1], sample_idx.shape[0]
         g = None if d_loss is None else d_loss.detach().float().reshape(1).contiguous()
         order, starts = inverse_list(sample_idx, nn_idx)
         d_tgt = torch.empty(F, Nv, 3, dtype=torch.float32, device=dev)
         d_src = torch.empty(Nv, 3, dtype=torch.float32, device=dev) if ctx.need_src else None
-        _check(lib.a3d_arap_backward_f32(_stream(), F, Nv, K, S, _p(src), _p(tgt), tgt.stride(0), _p(nn_idx), _p(weight), _p(sample_idx),
-                                         _p(rot), _p(order), _p(starts), _p(g), _p(d_tgt), _p(d_src)), "a3d_arap_backward_f32")
+        launch("a3d_arap_backward_f32", dev, F, Nv, K, S, _p(src), _p(tgt), tgt.stride(0), _p(nn_idx), _p(weight), _p(sample_idx), _p(rot),
+               _p(order), _p(starts), _p(g), _p(d_tgt), _p(d_src))
         return d_src, d_tgt, None, None, None, None
 
 
@@ -183,10 +163,9 @@ def arap_energy(source: torch.Tensor, targets: torch.Tensor, nn_idx: torch.Tenso
     """The ARAP loss of ``targets [F, Nv, 3]`` against ``source [Nv, 3]`` over the graph ``nn_idx [Nv, K]`` (-1: no edge): a 0-d fp32 tensor,
     with ``return_rotations`` also ``R [F, S, 3, 3]``.  Semantics, gradients and guarantees: the module docstring.  Neither the forward nor
     the backward synchronises with the host."""
-    _require_f32_cuda("source", source)
-    _require_f32_cuda("targets", targets)
-    if not (isinstance(nn_idx, torch.Tensor) and nn_idx.is_cuda and nn_idx.dtype in (torch.int32, torch.int64)):
-        raise RuntimeError("nn_idx: expected an int32 / int64 CUDA tensor (no CPU fallback)")
+    require_f32_cuda("source", source)
+    require_f32_cuda("targets", targets)
+    require_index_cuda("nn_idx", nn_idx)
     Nv = source.shape[0]
     if source.dim() != 2 or source.shape[1] != 3 or targets.dim() != 3 or tuple(targets.shape[1:]) != (Nv, 3):
         raise ValueError(f"expected source [Nv, 3] and targets [F, Nv, 3], got {tuple(source.shape)} and {tuple(targets.shape)}")
@@ -201,7 +180,7 @@ def arap_energy(source: torch.Tensor, targets: torch.Tensor, nn_idx: torch.Tenso
     dev = source.device
     nn32 = nn_idx.detach().to(torch.int32).contiguous()
     if weight is not None:
-        _require_f32_cuda("weight", weight)
+        require_f32_cuda("weight", weight)
         if tuple(weight.shape) != (Nv, K):
             raise ValueError(f"weight: expected {(Nv, K)}, got {tuple(weight.shape)}")
         weight = weight.detach().contiguous()
@@ -218,8 +197,7 @@ def arap_energy(source: torch.Tensor, targets: torch.Tensor, nn_idx: torch.Tenso
     if F == 0 or S == 0:                                        # a sequence of the source alone: the reference's loop does not run
         loss = (source.sum() + targets.sum()) * 0.0
         return (loss, torch.empty(F, S, 3, 3, dtype=torch.float32, device=dev)) if return_rotations else loss
-    with torch.cuda.device(dev):
-        loss, rot = _ArapEnergy.apply(source, targets, nn32, weight, sample_idx, bool(return_rotations))
+    loss, rot = _ArapEnergy.apply(source, targets, nn32, weight, sample_idx, bool(return_rotations))
     return (loss, rot) if return_rotations else loss
 
 
@@ -254,7 +232,7 @@ def cal_connectivity_from_points(points=None, radius=0.1, K=10, trajectory=None,
         raise NotImplementedError("trajectory=: only the graph of the points themselves is supported")
     if mode != "nn":
         raise NotImplementedError(f"mode={mode!r}: only 'nn' is supported")
-    _require_f32_cuda("points", points)
+    require_f32_cuda("points", points)
     if points.dim() != 3 or points.shape[2] != 3:
         raise ValueError(f"points: expected [T, Nv, 3], got {tuple(points.shape)}")
     nn_idx, nn_dist = knn_graph(points[0], K)
@@ -283,7 +261,7 @@ def cal_arap_error(nodes_sequence, ii, jj, nn, K=10, weight=None, sample_num=512
                    return_rotations=False):
     """Drop-in for util.py:185-215: ``nodes_sequence [Nt, Nv, 3]``, frame 0 the source.  The keyword-only arguments are additions
     (the reference draws its sample on the host inside the function)."""
-    _require_f32_cuda("nodes_sequence", nodes_sequence)
+    require_f32_cuda("nodes_sequence", nodes_sequence)
     Nv = nodes_sequence.shape[1]
     nn_idx = edges_to_dense(ii, jj, nn, Nv, K)
     return arap_energy(nodes_sequence[0], nodes_sequence[1:], nn_idx, weight=weight, sample_idx=sample_idx, sample_num=sample_num,

@@ -16,7 +16,7 @@
 //   bwd_frame           per frame: partials in order; Euler / sigmoid / global MLPs backward; d mean / N; global weight gradients per frame
 //   bwd                 per (frame, 512 Gaussians), 128 threads: recompute, three MLPs backward; d hidden [T, N, 32]; per-frame d scaling /
 //                       d rotation; weight gradients as outer products summed over the block through LDS in row order, one slab per block
-//   wreduce             slabs of a frame in block order -> per-frame weight gradients; sum_rows adds frames in order
+//   wreduce             slabs of a frame in block order -> per-frame weight gradients; sum_leading (f32_common.h) adds frames in order
 //   bwd_spatial         per Gaussian: d sp = sum over frames (in order) of d hidden * time product; per spatial plane sample gradient [N, 3, 32]
 //   sgather / tgather   gather-form plane gradients: per texel (per frame row for the time planes), the Gaussians of the adjacent cells in
 //                       the cached stable-sorted order, split over a fixed number of slices that are added in slice order
@@ -24,7 +24,7 @@
 // No atomics anywhere: gradients are bitwise reproducible and independent of how images map to frames.
 //
 // Only fp32 entry points: compiled out of the fp16-storage pass of build.py so they are exported once.
-#include "common.h"
+#include "f32_common.h"
 
 #ifndef A3D_STORAGE_F16
 namespace {
@@ -705,14 +705,6 @@ __global__ __launch_bounds__(DG_BLOCK) void dg_wreduce_kernel(DgArgs a, const fl
   wf[(int64_t)f * 5 * DG_NETW + e] = s;
 }
 
-__global__ __launch_bounds__(DG_BLOCK) void dg_sum_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows, int64_t M) {
-  const int64_t k = (int64_t)blockIdx.x * DG_BLOCK + threadIdx.x;
-  if (k >= M) return;
-  float s = 0.f;
-  for (int r = 0; r < rows; ++r) s += src[r * M + k];
-  dst[k] = s;
-}
-
 // dspat [N, 3, 32]: cotangent of the sample of spatial plane (x,y) / (x,z) / (y,z), both scales
 __global__ __launch_bounds__(DG_BLOCK) void dg_bwd_spatial_kernel(DgArgs a, const float* __restrict__ dh, float* __restrict__ dspat) {
   const int n = blockIdx.x * DG_BLOCK + threadIdx.x;
@@ -848,7 +840,6 @@ __global__ __launch_bounds__(DG_BLOCK) void dg_tcombine_kernel(DgArgs a, int k, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-inline unsigned dg_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 inline int64_t dg_up4(int64_t v) { return (v + 3) & ~int64_t(3); }
 
 bool dg_planes(const int64_t* desc, DgPlanes& P) {        // desc: host [36] = off[12] | W[12] | H[12]
@@ -899,7 +890,7 @@ bool dg_args(DgArgs& a, int T, int N, int B, const float* xyz, const float* scal
 extern "C" int a3d_dg_cells_f32(a3d_stream_t stream, int N, const float* xyz, const int64_t* plane_desc, int* cells) {
   DgPlanes P;
   if (N <= 0 || !xyz || !cells || !a3d_aligned(4, xyz, cells) || !dg_planes(plane_desc, P)) return A3D_EINVAL;
-  dg_cells_kernel<<<dg_blocks(N, DG_BLOCK), DG_BLOCK, 0, (hipStream_t)stream>>>(N, xyz, P, cells);
+  dg_cells_kernel<<<blocks_for(N, DG_BLOCK), DG_BLOCK, 0, (hipStream_t)stream>>>(N, xyz, P, cells);
   return a3d_launch_status();
 }
 
@@ -960,10 +951,10 @@ extern "C" int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, con
     return (int)e;
   }
   dg_bwd_kernel<<<dim3(w.nblk, T), DG_BWD_BLOCK, 0, st>>>(a, sp, glob, dgm, d_means, d_scales, d_rots, dh, dsc, drot, wpart);
-  dg_wreduce_kernel<<<dim3(dg_blocks(3 * DG_NETW, DG_BLOCK), T), DG_BLOCK, 0, st>>>(a, wpart, w.nblk, wf);
-  dg_sum_rows_kernel<<<dg_blocks(5 * DG_NETW, DG_BLOCK), DG_BLOCK, 0, st>>>(wf, d_weights, T, 5 * DG_NETW);
-  dg_sum_rows_kernel<<<dg_blocks((int64_t)N * 3, DG_BLOCK), DG_BLOCK, 0, st>>>(dsc, d_scaling, T, (int64_t)N * 3);
-  dg_sum_rows_kernel<<<dg_blocks((int64_t)N * 4, DG_BLOCK), DG_BLOCK, 0, st>>>(drot, d_rotation, T, (int64_t)N * 4);
+  dg_wreduce_kernel<<<dim3(blocks_for(3 * DG_NETW, DG_BLOCK), T), DG_BLOCK, 0, st>>>(a, wpart, w.nblk, wf);
+  sum_leading(st, wf, d_weights, T, 5 * DG_NETW);
+  sum_leading(st, dsc, d_scaling, T, (int64_t)N * 3);
+  sum_leading(st, drot, d_rotation, T, (int64_t)N * 4);
   dg_bwd_spatial_kernel<<<w.chunks, DG_BLOCK, 0, st>>>(a, dh, dspat);
   tw.woff[0] = 0;
   for (int s = 0, i = 0; s < 2; ++s)
@@ -972,7 +963,7 @@ extern "C" int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, con
   for (int s = 0, i = 0; s < 2; ++s)
     for (int p : {2, 4, 5}) {
       const int k = 6 * s + p;
-      dg_tcombine_kernel<<<dg_blocks((int64_t)a.P.W[k] * a.P.H[k] * DG_C, DG_BLOCK), DG_BLOCK, 0, st>>>(a, k, tw.woff[i], w.sumW, rows, d_grid);
+      dg_tcombine_kernel<<<blocks_for((int64_t)a.P.W[k] * a.P.H[k] * DG_C, DG_BLOCK), DG_BLOCK, 0, st>>>(a, k, tw.woff[i], w.sumW, rows, d_grid);
       ++i;
     }
   for (int s = 0; s < 2; ++s) {

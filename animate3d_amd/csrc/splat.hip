@@ -10,11 +10,11 @@
 //   render_bwd       same tiling, back to front; each Gaussian's gradient is summed over the tile's 256 pixels on chip (DPP within rows of 16
 //                    lanes, readlane across rows, LDS across the four waves) and stored as ONE row per instance, in duplicated order
 //   preprocess_bwd   one thread per (image, Gaussian): sums its contiguous span of instance rows in a fixed order, chains to the inputs
-//   sum_batch        inputs shared by all images ([N, ...]) get their gradient summed over B in a fixed order
+//   sum_batch        inputs shared by all images ([N, ...]) get their gradient summed over B in a fixed order (f32_common.h: sum_leading)
 // No atomics anywhere: gradients are bitwise reproducible.
 //
 // Only fp32 entry points: compiled out of the fp16-storage pass of build.py so they are exported once.
-#include "common.h"
+#include "f32_common.h"
 
 #ifndef A3D_STORAGE_F16
 namespace {
@@ -605,16 +605,6 @@ __global__ __launch_bounds__(256) void gs_preprocess_bwd_kernel(GsInputs in, con
   d_opac[idx] = vis ? g[5] : 0.f;
 }
 
-__global__ __launch_bounds__(256) void gs_sum_batch_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int64_t M) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= M) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += src[b * M + k];
-  dst[k] = s;
-}
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 inline bool gs_inputs_ok(const GsInputs& in) {
   if (in.B <= 0 || in.N <= 0 || in.H <= 0 || in.W <= 0 || (int64_t)in.B * in.N > 0x7fffffffLL) return false;
   if (!in.means || !in.scales || !in.rots || !in.opac || !in.view || !in.proj || !in.campos || !in.tanfovx || !in.tanfovy) return false;
@@ -714,7 +704,7 @@ extern "C" int a3d_gs_preprocess_bwd_f32(a3d_stream_t stream, A3D_GS_INPUT_PARAM
 
 extern "C" int a3d_gs_sum_batch_f32(a3d_stream_t stream, const float* src, float* dst, int B, int64_t M) {
   if (!src || !dst || B <= 0 || M <= 0) return A3D_EINVAL;
-  gs_sum_batch_kernel<<<blocks_for(M), 256, 0, (hipStream_t)stream>>>(src, dst, B, M);
+  sum_leading((hipStream_t)stream, src, dst, B, M);
   return a3d_launch_status();
 }
 #endif  // A3D_STORAGE_F16

@@ -49,23 +49,19 @@ from __future__ import annotations
 
 import ctypes
 import itertools
-import weakref
 from typing import Dict, Optional, Sequence
 
 import torch
 from torch import nn
 
-from .hip_ops import _check, _p, load_library
+from .f32_stage import TensorKeyed, gather_plan, launch, require_f32_cuda
+from .hip_ops import _p, load_library
 
 PAIRS = tuple(itertools.combinations(range(4), 2))          # (x,y) (x,z) (x,t) (y,z) (y,t) (z,t)
 CHANNELS, SCALES, NEURONS, NET_FLOATS = 16, 2, 32, 1152
 LOCAL_NETS = ("delta_xyz_network", "delta_rot_network", "delta_scaling_network")
 GLOBAL_NETS = ("global_rot_network", "global_trans_network")
 NET_OUT = {"delta_xyz_network": 3, "delta_rot_network": 4, "delta_scaling_network": 3, "global_rot_network": 3, "global_trans_network": 3}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def plane_dims(grid_size: Sequence[Sequence[int]]):
@@ -105,35 +101,29 @@ def _plane_desc(grid_size):
 
 def build_plan(cells: torch.Tensor, n_cells: Sequence[int]):
     """cells [12, N] -> (order [12, N] int32: Gaussians stable-sorted by cell; starts: per plane cells + 1 first positions, back to back)."""
-    orders, starts = [], []
-    for k, nc in enumerate(n_cells):
-        srt, order = torch.sort(cells[k].long(), stable=True)
-        orders.append(order.to(torch.int32))
-        starts.append(torch.searchsorted(srt, torch.arange(nc + 1, device=cells.device)).to(torch.int32))
+    orders, starts = zip(*(gather_plan(cells[k], nc) for k, nc in enumerate(n_cells)))
     return torch.stack(orders).contiguous(), torch.cat(starts).contiguous()
 
 
-class BinningPlan:
+def _grid_key(grid_size):
+    return tuple(tuple(int(v) for v in r) for r in grid_size)
+
+
+class BinningPlan(TensorKeyed):
     """The gather plan of the plane gradients for one ``xyz``; ``matches`` tells whether it still describes a tensor."""
 
     def __init__(self, xyz: torch.Tensor, grid_size):
-        lib = load_library()
         desc, _, _ = _plane_desc(grid_size)
         N = xyz.shape[0]
         x = xyz.detach().contiguous()
         cells = torch.empty(12, N, dtype=torch.int32, device=xyz.device)
-        _check(lib.a3d_dg_cells_f32(_stream(), N, _p(x), desc, _p(cells)), "a3d_dg_cells_f32")
+        launch("a3d_dg_cells_f32", xyz.device, N, _p(x), desc, _p(cells))
         self.cells = cells                                       # [12, N] as a3d_dg_cells_f32 assigned them
         self.order, self.starts = build_plan(cells, plane_cells(grid_size))
-        self.key = self._key(xyz, grid_size)
-        self._xyz = weakref.ref(xyz)                             # the address alone could be a later tensor on the same allocator block
-
-    @staticmethod
-    def _key(xyz, grid_size):
-        return (xyz.data_ptr(), xyz._version, tuple(xyz.shape), str(xyz.device), tuple(tuple(int(v) for v in r) for r in grid_size))
+        self.bind(xyz, _grid_key(grid_size))
 
     def matches(self, xyz, grid_size) -> bool:
-        return self._xyz() is xyz and self.key == self._key(xyz, grid_size)
+        return super().matches(xyz, _grid_key(grid_size))
 
 
 def _pack_weights(nets: Dict[str, Sequence[torch.Tensor]], device) -> torch.Tensor:
@@ -169,8 +159,8 @@ class _DeformGaussians(torch.autograd.Function):
             mpart = torch.empty(T, int(lib.a3d_dg_mean_partials(N)), 32, **f32)
             gmean, glob = torch.zeros(T, 32, **f32), torch.zeros(T, 12, **f32)
         means, scales, rots = torch.empty(B, N, 3, **f32), torch.empty(B, N, 3, **f32), torch.empty(B, N, 4, **f32)
-        _check(lib.a3d_dg_forward_f32(_stream(), T, N, B, _p(x), _p(sc), _p(ro), _p(ts), _p(packed), desc, _p(w), flags, _p(img_start),
-                                      _p(img_list), _p(sp), _p(mpart), _p(gmean), _p(glob), _p(means), _p(scales), _p(rots)), "a3d_dg_forward_f32")
+        launch("a3d_dg_forward_f32", dev, T, N, B, _p(x), _p(sc), _p(ro), _p(ts), _p(packed), desc, _p(w), flags, _p(img_start), _p(img_list),
+               _p(sp), _p(mpart), _p(gmean), _p(glob), _p(means), _p(scales), _p(rots))
         ctx.save_for_backward(x, sc, ro, ts, packed, w, img_start, img_list, sp, gmean, glob, plan.order, plan.starts)
         ctx.meta = (T, N, B, flags, grid_size, offs, total, net_names, [g.shape for g in grids], [p.shape for p in weights])
         return means, scales, rots
@@ -186,9 +176,9 @@ class _DeformGaussians(torch.autograd.Function):
         ws = torch.empty(int(lib.a3d_dg_backward_ws_floats(T, N, desc)), **f32)
         d_grid, d_w = torch.empty(total, **f32), torch.empty(5, NET_FLOATS, **f32)
         d_scaling, d_rotation = torch.empty(N, 3, **f32), torch.empty(N, 4, **f32)
-        _check(lib.a3d_dg_backward_f32(_stream(), T, N, B, _p(x), _p(sc), _p(ro), _p(ts), _p(packed), desc, _p(w), flags, _p(img_start),
-                                       _p(img_list), _p(sp), _p(gmean), _p(glob), _p(order), _p(starts), _p(cot[0]), _p(cot[1]), _p(cot[2]),
-                                       _p(ws), _p(d_grid), _p(d_w), _p(d_scaling), _p(d_rotation)), "a3d_dg_backward_f32")
+        launch("a3d_dg_backward_f32", dev, T, N, B, _p(x), _p(sc), _p(ro), _p(ts), _p(packed), desc, _p(w), flags, _p(img_start), _p(img_list),
+               _p(sp), _p(gmean), _p(glob), _p(order), _p(starts), _p(cot[0]), _p(cot[1]), _p(cot[2]), _p(ws), _p(d_grid), _p(d_w),
+               _p(d_scaling), _p(d_rotation))
         grads = []
         for off, shp in zip(offs, grid_shapes):
             _, C, H, W = shp
@@ -210,8 +200,7 @@ def deform_gaussians(xyz: torch.Tensor, scaling: torch.Tensor, rotation: torch.T
     """``grids``: two sequences of six planes; ``networks``: {name: (layers.0.weight, layers.2.weight)} with the three ``delta_*`` networks
     and, for ``use_global_trans``, the two ``global_*`` ones.  Returns (means [B, N, 3], scales [B, N, 3], rotations [B, N, 4])."""
     for name, t in (("xyz", xyz), ("scaling", scaling), ("rotation", rotation), ("timestamps", timestamps)):
-        if not (t.is_cuda and t.dtype == torch.float32):
-            raise RuntimeError(f"{name}: expected a float32 CUDA tensor, got {t.dtype} on {t.device} (no CPU fallback)")
+        require_f32_cuda(name, t)
     if xyz.requires_grad:
         raise NotImplementedError("xyz.requires_grad: the 4-D stage keeps the positions fixed; no gradient reaches the sampling coordinates")
     N = xyz.shape[0]
@@ -268,7 +257,7 @@ class HexPlaneDeformation(nn.Module):
     def __init__(self, grid_size=((50, 50, 50, 8), (100, 100, 100, 16)), n_grid_dims: int = 16, use_global_trans: bool = False,
                  n_neurons: int = 32, n_hidden_layers: int = 1):
         super().__init__()
-        grid_size = tuple(tuple(int(v) for v in r) for r in grid_size)
+        grid_size = _grid_key(grid_size)
         _check_config(grid_size, n_grid_dims, n_neurons, n_hidden_layers)
         self.grid_size, self.use_global_trans = grid_size, bool(use_global_trans)
         self.grids = nn.ModuleList()
@@ -293,8 +282,7 @@ class HexPlaneDeformation(nn.Module):
         return self._plan
 
     def forward(self, xyz, scaling, rotation, timestamps, image_to_time=None, deform_scales: bool = True, first_frame_trainable: bool = False):
-        if not (xyz.is_cuda and xyz.dtype == torch.float32):
-            raise RuntimeError(f"xyz: expected a float32 CUDA tensor, got {xyz.dtype} on {xyz.device} (no CPU fallback)")
+        require_f32_cuda("xyz", xyz)
         if xyz.requires_grad:
             raise NotImplementedError("xyz.requires_grad: the 4-D stage keeps the positions fixed")
         names = LOCAL_NETS + (GLOBAL_NETS if self.use_global_trans else ())

@@ -40,15 +40,12 @@ from typing import NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from .hip_ops import _check, _p, load_library
+from .f32_stage import launch, require_f32_cuda
+from .hip_ops import _p
 
 TILE = 16
 ROW_FLOATS = 12          # per-instance gradient row of a3d_gs_render_bwd_f32
 _stats = {"instances": 0}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def tile_grid(height: int, width: int):
@@ -78,8 +75,7 @@ def last_instance_count() -> int:
 
 
 def _per_gaussian(t: torch.Tensor, name: str, B: int, N: int, tail: Sequence[int]):
-    if not (t.is_cuda and t.dtype == torch.float32):
-        raise RuntimeError(f"{name}: expected a float32 CUDA tensor, got {t.dtype} on {t.device} (no CPU fallback)")
+    require_f32_cuda(name, t)
     tail = tuple(tail)
     if tuple(t.shape) == (N, *tail):
         return t.contiguous(), 0
@@ -104,7 +100,7 @@ def _reduce_to(g: torch.Tensor, shape: torch.Size, B: int) -> torch.Tensor:
     if B == 1:
         return g.reshape(shape)
     out = torch.empty(shape, dtype=torch.float32, device=g.device)
-    _check(load_library().a3d_gs_sum_batch_f32(_stream(), _p(g), _p(out), B, out.numel()), "a3d_gs_sum_batch_f32")
+    launch("a3d_gs_sum_batch_f32", g.device, _p(g), _p(out), B, out.numel())
     return out
 
 
@@ -112,7 +108,6 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, opacities, shs, colors_precomp, means2D, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
                 bg, image_height, image_width, scale_modifier, sh_degree):
-        lib = load_library()
         B, N, H, W = viewmatrix.shape[0], means3D.shape[-2], int(image_height), int(image_width)
         dev = means3D.device
         m, m_bs = _per_gaussian(means3D.detach(), "means3D", B, N, (3,))
@@ -135,13 +130,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         bgc = bg.detach().float().reshape(3).contiguous()
         inputs = (B, N, _p(m), m_bs, _p(s), s_bs, _p(r), r_bs, _p(o), o_bs, _p(sh), sh_bs, M, int(sh_degree), _p(col), col_bs,
                   _p(view), _p(proj), _p(cam), _p(tanfovx), _p(tanfovy), H, W, float(scale_modifier))
-        stream = _stream()
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         radii, clamped, tiles = torch.empty(B, N, **i32), torch.empty(B, N, **i32), torch.empty(B, N, **i32)
         xy, depth, conic, rgb = torch.empty(B, N, 2, **f32), torch.empty(B, N, **f32), torch.empty(B, N, 4, **f32), torch.empty(B, N, 3, **f32)
-        _check(lib.a3d_gs_preprocess_f32(stream, *inputs, _p(radii), _p(xy), _p(depth), _p(conic), _p(rgb), _p(clamped), _p(tiles)),
-               "a3d_gs_preprocess_f32")
+        launch("a3d_gs_preprocess_f32", dev, *inputs, _p(radii), _p(xy), _p(depth), _p(conic), _p(rgb), _p(clamped), _p(tiles))
         offsets = torch.cumsum(tiles.view(-1), 0)
         L = int(offsets[-1])
         if L >= 2 ** 31:
@@ -149,19 +142,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         _stats["instances"] = L
         keys = torch.empty(max(L, 1), dtype=torch.int64, device=dev)
         vals = torch.empty(max(L, 1), **i32)
-        _check(lib.a3d_gs_duplicate_f32(stream, B, N, H, W, _p(xy), _p(depth), _p(radii), _p(offsets), _p(keys), _p(vals)),
-               "a3d_gs_duplicate_f32")
+        launch("a3d_gs_duplicate_f32", dev, B, N, H, W, _p(xy), _p(depth), _p(radii), _p(offsets), _p(keys), _p(vals))
         keys_sorted, perm = torch.sort(keys[:L], stable=True)
         if L == 0:
             perm = torch.zeros(1, dtype=torch.int64, device=dev)
         gx, gy = tile_grid(H, W)
         ranges = torch.empty(B * gx * gy, 2, **i32)
-        _check(lib.a3d_gs_tile_ranges_f32(stream, _p(keys_sorted), L, _p(ranges), B * gx * gy), "a3d_gs_tile_ranges_f32")
+        launch("a3d_gs_tile_ranges_f32", dev, _p(keys_sorted), L, _p(ranges), B * gx * gy)
         img, dep, alpha, T_final = (torch.empty(B, 3, H, W, **f32), torch.empty(B, 1, H, W, **f32), torch.empty(B, 1, H, W, **f32),
                                     torch.empty(B, H, W, **f32))
         n_contrib = torch.empty(B, H, W, **i32)
-        _check(lib.a3d_gs_render_f32(stream, B, N, H, W, _p(ranges), _p(perm), _p(vals), _p(xy), _p(conic), _p(rgb), _p(depth), _p(bgc),
-                                     _p(img), _p(dep), _p(alpha), _p(T_final), _p(n_contrib)), "a3d_gs_render_f32")
+        launch("a3d_gs_render_f32", dev, B, N, H, W, _p(ranges), _p(perm), _p(vals), _p(xy), _p(conic), _p(rgb), _p(depth), _p(bgc), _p(img),
+               _p(dep), _p(alpha), _p(T_final), _p(n_contrib))
         ctx.save_for_backward(m, s, r, o, sh, col, view, proj, cam, tanfovx, tanfovy, bgc, radii, clamped, tiles, offsets, ranges, perm,
                               vals, xy, conic, rgb, depth, T_final, n_contrib)
         ctx.meta = (B, N, H, W, M, int(sh_degree), float(scale_modifier), m_bs, s_bs, r_bs, o_bs, sh_bs, col_bs, L)
@@ -175,22 +167,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         (m, s, r, o, sh, col, view, proj, cam, tanfovx, tanfovy, bgc, radii, clamped, tiles, offsets, ranges, perm, vals, xy, conic, rgb,
          depth, T_final, n_contrib) = ctx.saved_tensors
         B, N, H, W, M, deg, smod, m_bs, s_bs, r_bs, o_bs, sh_bs, col_bs, L = ctx.meta
-        lib, stream, dev = load_library(), _stream(), m.device
+        dev = m.device
         f32 = dict(dtype=torch.float32, device=dev)
         d_img = torch.zeros(B, 3, H, W, **f32) if d_img is None else d_img.float().contiguous()
         d_depth = None if d_depth is None else d_depth.float().contiguous()
         d_alpha = None if d_alpha is None else d_alpha.float().contiguous()
         rows = torch.empty(max(L, 1), ROW_FLOATS, **f32)
-        _check(lib.a3d_gs_render_bwd_f32(stream, B, N, H, W, _p(ranges), _p(perm), _p(vals), _p(xy), _p(conic), _p(rgb), _p(depth), _p(bgc),
-                                         _p(T_final), _p(n_contrib), _p(d_img), _p(d_depth), _p(d_alpha), _p(rows)), "a3d_gs_render_bwd_f32")
+        launch("a3d_gs_render_bwd_f32", dev, B, N, H, W, _p(ranges), _p(perm), _p(vals), _p(xy), _p(conic), _p(rgb), _p(depth), _p(bgc),
+               _p(T_final), _p(n_contrib), _p(d_img), _p(d_depth), _p(d_alpha), _p(rows))
         g2d, gm, gs, gr, go = (torch.empty(B, N, 3, **f32), torch.empty(B, N, 3, **f32), torch.empty(B, N, 3, **f32), torch.empty(B, N, 4, **f32),
                                torch.empty(B, N, 1, **f32))
         gsh = torch.empty(B, N, M, 3, **f32) if sh is not None else None
         gcol = torch.empty(B, N, 3, **f32) if col is not None else None
         inputs = (B, N, _p(m), m_bs, _p(s), s_bs, _p(r), r_bs, _p(o), o_bs, _p(sh), sh_bs, M, deg, _p(col), col_bs,
                   _p(view), _p(proj), _p(cam), _p(tanfovx), _p(tanfovy), H, W, smod)
-        _check(lib.a3d_gs_preprocess_bwd_f32(stream, *inputs, _p(radii), _p(clamped), _p(offsets), _p(tiles), _p(rows), _p(g2d), _p(gm), _p(gs),
-                                             _p(gr), _p(go), _p(gsh), _p(gcol)), "a3d_gs_preprocess_bwd_f32")
+        launch("a3d_gs_preprocess_bwd_f32", dev, *inputs, _p(radii), _p(clamped), _p(offsets), _p(tiles), _p(rows), _p(g2d), _p(gm), _p(gs),
+               _p(gr), _p(go), _p(gsh), _p(gcol))
         m_shape, s_shape, r_shape, o_shape, sh_shape, col_shape, m2_shape = ctx.shapes
         need = ctx.needs_input_grad
         out_m = _reduce_to(gm, m_shape, B) if need[0] else None

@@ -179,6 +179,20 @@ def test_xyz_gradient_refused_and_plan_follows_in_place_changes():
     assert all(torch.equal(a, b) for a, b in zip(o2, o3)) and all(torch.equal(a, b) for a, b in zip(g2, g3))
 
 
+def test_plan_stops_matching_after_an_in_place_change_of_equal_value():
+    """The plan's key holds the tensor's version: ``add_(0)`` leaves every value and the address as they were, and the plan is rebuilt."""
+    m = _module(False)
+    xyz, _, _ = _inputs(64, 7)
+    plan = m.plan_for(xyz)
+    assert isinstance(plan, deform4d.BinningPlan) and plan.matches(xyz, RELEASED) and m.plan_for(xyz) is plan
+    assert not plan.matches(xyz, ((50, 50, 50, 8), (100, 100, 100, 8)))
+    xyz.add_(0)
+    assert not plan.matches(xyz, RELEASED)
+    again = m.plan_for(xyz)
+    assert again is not plan and again.matches(xyz, RELEASED)
+    assert torch.equal(again.cells, plan.cells) and torch.equal(again.order, plan.order) and torch.equal(again.starts, plan.starts)
+
+
 def test_sds_config5_step_from_deformation_field_gpu():
     """BASELINE config 5 one link earlier than test_sds_config5_step_from_gaussians_gpu: HexPlaneDeformation -> rasterize_gaussians ->
     sds_guidance_loss -> loss.backward() fills every plane and every MLP weight; one Adam step on them changes the rendered image."""

@@ -16,21 +16,7 @@ import torch
 
 from animate3d_amd import arap
 from tests import arap_ref
-
-
-def timed(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e))
-    ts.sort()
-    return ts[len(ts) // 2]
+from tools._timing import timed
 
 
 def torch_knn(x, K, chunk=4096):

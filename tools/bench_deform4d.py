@@ -15,31 +15,7 @@ import torch
 
 from animate3d_amd import deform4d
 from tests import deform_ref
-
-
-
-def timed(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e))
-    ts.sort()
-    return ts[len(ts) // 2]
-
-
-def peak_mib(fn):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+from tools._timing import peak_mib, timed
 
 
 def main():

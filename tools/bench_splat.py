@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from animate3d_amd import splat
+from tools._timing import timed
 
 
 def scene(N, B, seed=0):
@@ -45,21 +46,6 @@ def scene(N, B, seed=0):
     cam = dict(viewmatrix=w2c, projmatrix=full, campos=center, tanfovx=torch.tan(fovy / 2), tanfovy=torch.tan(fovy / 2),
                image_height=256, image_width=256, bg=torch.ones(3, device="cuda"), sh_degree=3)
     return p, cam
-
-
-def timed(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e))
-    ts.sort()
-    return ts[len(ts) // 2]
 
 
 def main():
