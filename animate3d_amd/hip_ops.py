@@ -135,6 +135,10 @@ _SIGNATURES = {
     "a3d_knn_f32": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_f32, c_vp, c_vp]),
     "a3d_arap_energy_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_arap_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins
+    "a3d_clip_preprocess_lds_limit": (c_i64, []),
+    "a3d_clip_preprocess": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,
+                                    c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp]),
 }
 # fp16-storage twins (include/animate3d_hip.h, last section): same signatures
 _UNSUFFIXED_TWINS = ("a3d_im2col_in", "a3d_unpack_out", "a3d_im2col_in_bwd")      # boundary kernels: the bf16 build has no suffix

@@ -98,15 +98,36 @@ def sds_recon_loss(unet, latents: torch.Tensor, t: torch.Tensor, text_embeddings
     return loss, {"latents_noisy": noisy_flat, "noise_pred": eps_cfg, "latents_recon": recon}
 
 
-def sds_guidance_loss(vae, unet, rgb: torch.Tensor, t: torch.Tensor, text_embeddings: torch.Tensor, image_embeds: torch.Tensor,
+def first_frame_index(b: int, n_view: int, n_frame: int, device) -> torch.Tensor:
+    """The positions of frame 0 of every (b, view) video in a ``(b n f)`` batch: ``arange(b * n_view) * n_frame``, int32 on ``device``
+    (``rearrange(x, "(b f) c h w -> b f c h w", f=n_frame)[:, 0]``, animatemv_guidance.py:547)."""
+    return torch.arange(b * n_view, device=device, dtype=torch.int32) * n_frame
+
+
+def sds_guidance_loss(vae, unet, rgb: torch.Tensor, t: torch.Tensor, text_embeddings: torch.Tensor, image_embeds: Optional[torch.Tensor],
                       c2w: Optional[torch.Tensor], *, rgb_as_latents: bool = False, vae_generator: Optional[torch.Generator] = None,
-                      vae_noise: Optional[torch.Tensor] = None, **sds_kw) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
-    """``AnimateMVDiffusionGuidance.__call__`` (animatemv_guidance.py:509-560) from the rendered frames to the loss, minus the CLIP image
-    encode (the caller passes ``image_embeds``: clip.py).  ``rgb`` [(b n f), H, W, 3] in [0, 1] -> bilinear resize to 256^2
-    (align_corners=False, :532-535) -> ``vae.encode_images`` (an ``AutoencoderKLEncoder``, :536-543) -> ``sds_recon_loss``.  With
-    ``rgb_as_latents`` (``rgb`` then has the 4 latent channels) the resize goes to 32^2 and the result is taken as the latents (:537-540).  ``vae_generator`` / ``vae_noise``: the
-    posterior sample's noise.  Returns (loss, aux) as ``sds_recon_loss`` does, with aux["latents"] the encoded latents;
-    ``loss.backward()`` fills ``rgb.grad`` through the encoder's input gradient."""
+                      vae_noise: Optional[torch.Tensor] = None, image_encoder=None, **sds_kw) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """``AnimateMVDiffusionGuidance.__call__`` (animatemv_guidance.py:509-560) from the rendered frames to the loss.  ``rgb`` [(b n f), H, W, 3]
+    in [0, 1] -> bilinear resize to 256^2 (align_corners=False, :532-535) -> ``vae.encode_images`` (an ``AutoencoderKLEncoder``, :536-543) ->
+    ``sds_recon_loss``.  With ``rgb_as_latents`` (``rgb`` then has the 4 latent channels) the resize goes to 32^2 and the result is taken as
+    the latents (:537-540).  ``vae_generator`` / ``vae_noise``: the posterior sample's noise.
+
+    The CLIP image condition (:546-555): pass ``image_embeds`` [b n, E], or pass None and ``image_encoder`` (a
+    ``clip.CLIPVisionEncoderWithProjection``): the embeddings then come from frame 0 of every video of ``rgb.detach()``, at the rendered
+    size, through ``clip.encode_image_from_frames`` (the reference's host copy, PIL and ``CLIPImageProcessor``, on the GPU and bit-equal).
+    Passing neither raises.
+
+    Returns (loss, aux) as ``sds_recon_loss`` does, with aux["latents"] the encoded latents; ``loss.backward()`` fills ``rgb.grad`` through
+    the encoder's input gradient."""
+    if image_embeds is None:
+        if image_encoder is None:
+            raise ValueError("sds_guidance_loss needs image_embeds or image_encoder")
+        from .clip import encode_image_from_frames
+        n, f = sds_kw.get("n_view", 4), sds_kw.get("n_frame", 8)
+        if rgb.shape[0] % (n * f) != 0:
+            raise ValueError(f"rgb batch {rgb.shape[0]} is not a multiple of n_view * n_frame = {n * f}")
+        first = first_frame_index(rgb.shape[0] // (n * f), n, f, rgb.device)
+        image_embeds = encode_image_from_frames(image_encoder, rgb.detach(), first)[0]
     x = rgb.permute(0, 3, 1, 2)
     if rgb_as_latents:
         latents = F.interpolate(x, (32, 32), mode="bilinear", align_corners=False)

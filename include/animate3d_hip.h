@@ -479,6 +479,27 @@ int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, int S, cons
                           const int* nn_idx, const float* weight, const int* sample_idx, const double* rot, const int* order,
                           const int* starts, const float* grad_out, float* d_targets, float* d_source);
 
+/* CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip; contract in animate3d_amd/clip.py, preprocess_frames).
+ * Replaces the device -> host -> PIL -> CLIPImageProcessor -> device round trip of animatemv_guidance.py:546-555 / utils/util.py:268-287,
+ * bit-equal to it: (uint8)(v * 255.0f), Pillow's 8-bit bicubic resampler (integer, 22 precision bits, horizontal then vertical pass, a
+ * clip to [0, 255] after each), the centre crop, and a [3, 256] table for /255 + mean / std.  One launch, one dtype code, no twins.
+ *   rgb            n_src frames [in_h, in_w, 3] of fp32, element (n, y, x, c) at rgb + n s_img + y s_y + x s_x + c s_c
+ *   image_index    [n_img] frames to take, or NULL (frame i); an index outside 0 .. n_src - 1 gives a frame of zero bytes
+ *   coef_* / bounds_* / ksize_*   per axis (x: horizontal pass, y: vertical) the fixed-point coefficients [crop, ksize] and
+ *                  (first input index, count) [crop, 2] of the crop x crop output window; ksize 0: the pass is skipped (equal sizes) and
+ *                  output i copies input off_* + i.  off_* is read only then
+ *   tile_rows      output rows per workgroup; max_rows: the most input rows the vertical pass of one such tile reads.  The tile's
+ *                  intermediate, max_rows * 3 * crop bytes, lives in LDS: above a3d_clip_preprocess_lds_limit() -> A3D_EUNSUPPORTED
+ *   table          [3, 256] fp32
+ *   outputs (each may be NULL, not all): pixel_values [n_img, 3, crop, crop] and patch_rows [n_img (crop / patch)^2, kp] with columns
+ *                  in (c, ky, kx) order and columns 3 patch^2 .. kp zero (needs tile_rows == patch, crop % patch == 0), both of `dtype`
+ *                  (A3D_F32 / A3D_BF16 / A3D_F16: one round-to-nearest-even of the table value); u8 [n_img, crop, crop, 3] the bytes */
+int64_t a3d_clip_preprocess_lds_limit(void);
+int a3d_clip_preprocess(a3d_stream_t stream, const float* rgb, int n_src, int in_h, int in_w, int64_t s_img, int64_t s_y, int64_t s_x,
+                        int64_t s_c, const int* image_index, int n_img, int crop, const int* coef_x, const int* bounds_x, int ksize_x,
+                        int off_x, const int* coef_y, const int* bounds_y, int ksize_y, int off_y, int tile_rows, int max_rows,
+                        const float* table, int dtype, void* pixel_values, void* patch_rows, int patch, int kp, uint8_t* u8);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
  * IEEE fp16 as the storage type (same signature, same semantics, same fp32 accumulation / statistics / softmax; the MFMA is
