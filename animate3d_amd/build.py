@@ -2,8 +2,8 @@
 
     python -m animate3d_amd.build            # incremental
     python -m animate3d_amd.build --force
-    python -m animate3d_amd.build --experiment A3D_EXP_CHUNK_MAJOR   # side build lib/exp/libanimate3d_hip_<macro>.so for
-                                                                      # tools/microbench.py (A3D_LIB=...); never loaded by the package
+    python -m animate3d_amd.build --experiment MACRO    # side build lib/exp/libanimate3d_hip_MACRO.so with -DMACRO on every source, for
+                                                         # tools/microbench.py and the pmc_* tools (A3D_LIB=...); never loaded by the package
 """
 from __future__ import annotations
 

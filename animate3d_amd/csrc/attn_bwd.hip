@@ -19,7 +19,7 @@
 // second, transposed image per tensor: every row tile was loaded from global twice and transposed with v_perm_b32 + 8-byte LDS writes).
 // The loads of the next row tile are issued into registers before the current tile's MFMAs and written to LDS after them; a wave owns
 // one or two 32-column sub-tiles (CT) that share every row-side LDS fragment.
-#include "common.h"
+#include "flash_common.h"
 
 #include <cfloat>
 #include <cmath>
@@ -38,7 +38,9 @@ struct BwdParams {
   float inv_do_scale;                     // 1 / do_scale, 0 for do_scale == 0 (the gradients vanish: no -0 * inf seed)
 };
 
-A3D_DEV int64_t map_row(const a3d_rowmap& m, int64_t g, int64_t s) {
+// the row maps in 64-bit arithmetic: the backward accepts sequence positions up to 2^31 (flash_common.h's map_row is the forward's, clamped
+// to 32 bits for positions below 2^30)
+A3D_DEV int64_t map_row64(const a3d_rowmap& m, int64_t g, int64_t s) {
   return (g / m.gdiv) * m.ga + (g % m.gdiv) * m.gb + (s / m.seg_len) * m.seg_stride + (s % m.seg_len);
 }
 // the same map with the group part hoisted: the staging loops evaluate it for every row of every tile, and a 64-bit
@@ -54,27 +56,6 @@ A3D_DEV GroupRows group_rows(const a3d_rowmap& m, int64_t g) {
 A3D_DEV int64_t row_of(const GroupRows& a, int s) {
   const uint32_t seg = (uint32_t)s / a.seg_len;
   return a.base + (int64_t)seg * a.seg_stride + (int64_t)((uint32_t)s - seg * a.seg_len);
-}
-
-// row (within a 32-row sub-tile) that feeds MFMA A-row i: result register r of a lane in half g then is row 16*(r>>3) + 8*g + (r&7)
-A3D_DEV int kperm(int i) {
-  const int j = i & 3, g = (i >> 2) & 1, b = i >> 3;
-  return 16 * (b >> 1) + 8 * g + 4 * (b & 1) + j;
-}
-
-// LDS-DMA: 64 lanes x 16 B -> LDS[lds_dst + 16 lane] under a wave-uniform lane mask; source = scalar base + per-lane byte offset.  Not counted by
-// the compiler: s_waitcnt vmcnt by hand (flash_common.h has the same helper for the forward kernels).
-A3D_DEV void bwd_glds16_m(uint32_t voff, const void* sbase, uint32_t lds_dst, uint64_t mask) {
-  unsigned keep;
-  uint64_t ex;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_mov_b64 %1, exec\n\ts_mov_b64 exec, %5\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep), "=&s"(ex) : "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)), "s"(mask) : "memory");
-}
-A3D_DEV const uint16_t* bwd_scalar(const uint16_t* ptr) {      // wave-uniform by construction; say so
-  const uint64_t a = (uint64_t)(uintptr_t)ptr;
-  return (const uint16_t*)(uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
-                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a));
 }
 
 // DMA (round 6): the row tiles go global -> LDS by LDS-DMA instead of through registers.  Timing ablations (profiles/r6_attn_bwd_ablations.log)
@@ -131,11 +112,11 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
     const int colc = col_ok[c] ? col[c] : clen - 1;
     const uint16_t* a_src; const uint16_t* b_src;
     if constexpr (MODE == MODE_DKV) {
-      const int64_t row = map_row(p.km, grp_c, colc);
+      const int64_t row = map_row64(p.km, grp_c, colc);
       a_src = p.K + row * p.km.ld + hoff; b_src = p.V + row * p.km.ld + hoff;
     } else {
-      a_src = p.Q + map_row(p.qm, grp_c, colc) * p.qm.ld + hoff;
-      b_src = p.dO + map_row(p.dom, grp_c, colc) * p.dom.ld + hoff;
+      a_src = p.Q + map_row64(p.qm, grp_c, colc) * p.qm.ld + hoff;
+      b_src = p.dO + map_row64(p.dom, grp_c, colc) * p.dom.ld + hoff;
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -218,16 +199,16 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
     };
     if constexpr (DMA) {
       // (tile t goes into buffer t & 1: the caller guarantees its last readers have passed a barrier)
-      const uint16_t* const ba = bwd_scalar(src_a + tile_a * ld_a);
-      const uint16_t* const bb = bwd_scalar(src_b + tile_b * ld_b);
+      const uint16_t* const ba = dm_scalar(src_a + tile_a * ld_a);
+      const uint16_t* const bb = dm_scalar(src_b + tile_b * ld_b);
       const uint32_t l1 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)(smem + (t & 1) * 2 * N_ELEMS);
       const uint32_t l2 = l1 + (uint32_t)N_ELEMS * 2u;
 #pragma unroll
       for (int i = 0; i < NIW; ++i) {
         const int j = wid + 4 * i;
         if (j < NI) {
-          bwd_glds16_m(voffA[i], ba, l1 + (uint32_t)j * 1024u, dmask[i]);
-          bwd_glds16_m(voffB[i], bb, l2 + (uint32_t)j * 1024u, dmask[i]);
+          dm_glds16_sm(voffA[i], ba, l1 + (uint32_t)j * 1024u, dmask[i]);
+          dm_glds16_sm(voffB[i], bb, l2 + (uint32_t)j * 1024u, dmask[i]);
         }
       }
     } else {
@@ -376,9 +357,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
     const uint16_t* const N1 = smem + (t & 1) * 2 * N_ELEMS;
     const uint16_t* const N2 = N1 + N_ELEMS;
     const float (*const rstat)[BR] = rstat_all[t & 1];
-#if !defined(A3D_EXP_BWD_NOSTAGE)
     if (t + 1 < total_tiles) load_tile(t + 1);
-#endif
     if constexpr (MODE == MODE_STATS) {
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
@@ -422,20 +401,9 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
         }
       });
     }
-#ifdef A3D_EXP_BWD_SINGLEBUF      // A/B build (python -m animate3d_amd.build --experiment A3D_EXP_BWD_SINGLEBUF): round 2's flow, two barriers per tile
-    __syncthreads();
-    if (t + 1 < total_tiles) store_tile((t + 1) & 1);
-    __syncthreads();
-#elif defined(A3D_EXP_BWD_NOSTAGE)      // timing ablations (results wrong): no row-tile loads / LDS stores after tile 0; == 2: no barrier either
-    if (t == 0) store_tile(1);
-#if A3D_EXP_BWD_NOSTAGE != 2
-    __syncthreads();
-#endif
-#else
     // tile t+1 goes into the other buffer: its last readers (tile t-1) passed the barrier of the previous iteration
     if (t + 1 < total_tiles) store_tile((t + 1) & 1);
     __syncthreads();
-#endif
   }
 
   // ---- results: lane holds column l31 of each sub-tile; register r = 4*qd + j of tile mt is dim d = 32*mt + 8*qd + 4*g + j
@@ -452,24 +420,8 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_kernel(const BwdParams p) {
     } else {
       if (!col_ok[c]) continue;
       auto write = [&](uint16_t* base, const a3d_rowmap& m, const f32x16_t (&acc)[MT], float mul) __attribute__((always_inline)) {
-        uint16_t* dst = base + map_row(m, grp_c, col[c]) * m.ld + hoff;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int qd = 0; qd < 4; ++qd) {
-            const int d0 = 32 * mt + 8 * qd + 4 * g;
-            if (d0 < D) {
-              float v0 = acc[mt][4 * qd] * mul, v1 = acc[mt][4 * qd + 1] * mul, v2 = acc[mt][4 * qd + 2] * mul, v3 = acc[mt][4 * qd + 3] * mul;
-              u32x2_t* o = reinterpret_cast<u32x2_t*>(dst + d0);
-              if (p.accumulate) {
-                const u32x2_t old = *o;
-                v0 += lo16(old[0]); v1 += hi16(old[0]); v2 += lo16(old[1]); v3 += hi16(old[1]);
-              }
-              u32x2_t w;
-              w[0] = pack16(v0, v1); w[1] = pack16(v2, v3);
-              *o = w;
-            }
-          }
+        store_acc8<D, MT>(base + map_row64(m, grp_c, col[c]) * m.ld + hoff, g, p.accumulate,
+                          [&](int mt, int r) __attribute__((always_inline)) { return acc[mt][r] * mul; });
       };
       if constexpr (MODE == MODE_DQ) {
         write(p.dQ, p.dqm, acc1[c], p.scale * p.do_scale);
@@ -497,11 +449,7 @@ int launch(hipStream_t s, const BwdParams& p, int groups_y) {
   const int rlen = (MODE == MODE_DKV) ? p.q_len : p.kv_len;
   // LDS-DMA staging: consecutive rows per tile, no clamped rows, 32-bit lane offsets, 16-byte aligned rows (checked by the entry point)
   const int64_t ld_max = p.qm.ld > p.km.ld ? (p.qm.ld > p.dom.ld ? p.qm.ld : p.dom.ld) : (p.km.ld > p.dom.ld ? p.km.ld : p.dom.ld);
-#ifdef A3D_EXP_BWD_NODMA
-  const bool dma = false;
-#else
   const bool dma = MODE != MODE_STATS && aligned && rlen % BR == 0 && (int64_t)BR * ld_max * 2 < (1ll << 31);
-#endif
   if (dma) attn_bwd_kernel<D, MODE, NU, CT, true, OCC, true><<<grid, dim3(256), 0, s>>>(p);
   else if (aligned) attn_bwd_kernel<D, MODE, NU, CT, true, OCC><<<grid, dim3(256), 0, s>>>(p);
   else attn_bwd_kernel<D, MODE, NU, CT, false, OCC><<<grid, dim3(256), 0, s>>>(p);
@@ -513,13 +461,9 @@ int launch(hipStream_t s, const BwdParams& p, int groups_y) {
 template <int MODE>
 int dispatch(hipStream_t s, const BwdParams& p, int head_dim, int groups_y) {
   switch (head_dim) {
-#ifdef A3D_EXP_BWD_NU2
-    case 40: return launch<40, MODE, 2, 1>(s, p, groups_y);      // measurement build: round 5's 64-row tiles
-#else
     // round 6: 128-row tiles at head_dim 40 (57 KB of LDS, still two workgroups per CU): half the barriers per score, 2.28 -> 2.12 ms per
     // level-0 backward (profiles/r6_microbench_attn_bwd.log); head_dim 80 would drop to one workgroup per CU (90 KB) and stays at 64 rows
     case 40: return launch<40, MODE, 4, 1>(s, p, groups_y);
-#endif
     case 64: return launch<64, MODE, 2, 1>(s, p, groups_y);
     case 80: return launch<80, MODE, 2, 1>(s, p, groups_y);
     case 160: return launch<160, MODE, 1, 1>(s, p, groups_y);
@@ -537,8 +481,8 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const uint16_t* __restr
   const int64_t grp = blockIdx.y;
   if (t >= (int64_t)q_len * heads) return;
   const int q = (int)(t / heads), h = (int)(t % heads);
-  const u32x4_t* a = reinterpret_cast<const u32x4_t*>(dO + map_row(dom, grp, q) * dom.ld + (int64_t)h * D);
-  const u32x4_t* b = reinterpret_cast<const u32x4_t*>(O + map_row(om, grp, q) * om.ld + (int64_t)h * D);
+  const u32x4_t* a = reinterpret_cast<const u32x4_t*>(dO + map_row64(dom, grp, q) * dom.ld + (int64_t)h * D);
+  const u32x4_t* b = reinterpret_cast<const u32x4_t*>(O + map_row64(om, grp, q) * om.ld + (int64_t)h * D);
   float acc = 0.f;
 #pragma unroll
   for (int i = 0; i < D / 8; ++i) {

@@ -583,27 +583,49 @@ void launch_two(bool aligned, int groups, hipStream_t s, const AttnParams& p) {
 
 }  // namespace
 
+// The argument check of the four forward entry points: refusals in one order (operands, maps, alignment, ranges, flags, shapes without a
+// kernel), then the launch parameters and `aligned` (every key tile lies inside one row-map segment).  `two`: a3d_flash_attn2's second key
+// set (K2, V2, kmap2, kv_len2, out_scale2); the others pass nullptr / 0 there.  `allowed`: the entry point's A3D_ATTN_* bits.
+static int attn_args(bool two, const void* Q, const void* K, const void* V, const void* K2, const void* V2, void* O,
+                     const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* kmap2, const a3d_rowmap* omap,
+                     int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len, int64_t kv_len2,
+                     float scale, float out_scale, float out_scale2, int flags, int allowed, AttnParams& p, bool& aligned) {
+  if (!Q || !K || !V || !O || groups <= 0 || heads <= 0 || q_len <= 0 || kv_len <= 0) return A3D_EINVAL;
+  if (two && (!K2 || !V2 || kv_len2 <= 0)) return A3D_EINVAL;
+  if (!map_ok(qmap, head_dim) || !map_ok(kmap, head_dim) || (two && !map_ok(kmap2, head_dim)) || !map_ok(omap, head_dim)) return A3D_EINVAL;
+  // Q, K, V rows are read 16 bytes at a time; O is written 8 bytes at a time (the kernels with 16-byte stores ask for more themselves)
+  if (!a3d_aligned(16, Q, K, V, K2, V2) || !a3d_aligned(8, O)) return A3D_EINVAL;
+  if (groups > 65535 || q_len > 0x3fffffffLL || kv_len > 0x3fffffffLL || kmap->seg_len > 0x3fffffffLL) return A3D_EINVAL;
+  if (two && (kv_len2 > 0x3fffffffLL || kmap2->seg_len > 0x3fffffffLL)) return A3D_EINVAL;
+  if (two && head_dim != 40 && head_dim != 80) return A3D_EUNSUPPORTED;
+  if (flags & ~allowed) return A3D_EINVAL;
+  p = AttnParams{};
+  p.Q = (const uint16_t*)Q; p.K = (const uint16_t*)K; p.V = (const uint16_t*)V; p.O = (uint16_t*)O;
+  p.qm = *qmap; p.km = *kmap; p.om = *omap;
+  p.heads = heads; p.q_len = (int)q_len; p.kv_len = (int)kv_len;
+  p.scale_log2 = scale * 1.4426950408889634f; p.out_scale = out_scale;
+  p.accumulate = flags & A3D_ATTN_ACCUMULATE; p.causal = (flags & A3D_ATTN_CAUSAL) != 0;
+  if (p.causal && head_dim != 64 && head_dim != 160) return A3D_EUNSUPPORTED;     // offered on the raw-score (fma) kernels only
+  const int bkv = head_dim == 160 ? 32 : 64;
+  aligned = (kmap->seg_len % bkv == 0) || (kv_len <= kmap->seg_len);
+  if (two) {
+    p.K2 = (const uint16_t*)K2; p.V2 = (const uint16_t*)V2; p.km2 = *kmap2; p.kv_len2 = (int)kv_len2; p.out_scale2 = out_scale2;
+    aligned = aligned && ((kmap2->seg_len % bkv == 0) || (kv_len2 <= kmap2->seg_len));
+  }
+  return A3D_OK;
+}
+
 static int flash_attn_impl(a3d_stream_t stream, const void* Q, const void* K, const void* V, void* O,
                            const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* omap,
                            int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len,
                            float scale, float out_scale, int accumulate, float* lse, unsigned int* counters = nullptr) {
-  if (!Q || !K || !V || !O || groups <= 0 || heads <= 0 || q_len <= 0 || kv_len <= 0) return A3D_EINVAL;
-  if (!map_ok(qmap, head_dim) || !map_ok(kmap, head_dim) || !map_ok(omap, head_dim)) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15u) return A3D_EINVAL;
-  if (reinterpret_cast<uintptr_t>(O) & 7u) return A3D_EINVAL;
-  if (groups > 65535 || q_len > 0x3fffffffLL || kv_len > 0x3fffffffLL || kmap->seg_len > 0x3fffffffLL) return A3D_EINVAL;
-  AttnParams p{};
-  p.Q = (const uint16_t*)Q; p.K = (const uint16_t*)K; p.V = (const uint16_t*)V; p.O = (uint16_t*)O;
-  p.qm = *qmap; p.km = *kmap; p.om = *omap;
-  p.heads = heads; p.q_len = (int)q_len; p.kv_len = (int)kv_len;
-  if (accumulate & ~(A3D_ATTN_ACCUMULATE | A3D_ATTN_CAUSAL | A3D_ATTN_EXACT | A3D_ATTN_PLAIN)) return A3D_EINVAL;
-  p.scale_log2 = scale * 1.4426950408889634f; p.out_scale = out_scale; p.accumulate = accumulate & 1; p.causal = (accumulate >> 1) & 1;
+  AttnParams p;
+  bool aligned;
+  if (int rc = attn_args(false, Q, K, V, nullptr, nullptr, O, qmap, kmap, nullptr, omap, groups, heads, head_dim, q_len, kv_len, 0,
+                         scale, out_scale, 0.f, accumulate, A3D_ATTN_ACCUMULATE | A3D_ATTN_CAUSAL | A3D_ATTN_EXACT | A3D_ATTN_PLAIN, p, aligned)) return rc;
   const bool exact = (accumulate & A3D_ATTN_EXACT) != 0, plain = (accumulate & A3D_ATTN_PLAIN) != 0;
   p.lse = lse;
   p.counters = counters;
-  if (p.causal && head_dim != 64 && head_dim != 160) return A3D_EUNSUPPORTED;     // offered on the raw-score (fma) kernels only
-  const int bkv = head_dim == 160 ? 32 : 64;
-  const bool aligned = (kmap->seg_len % bkv == 0) || (kv_len <= kmap->seg_len);
   hipStream_t s = (hipStream_t)stream;
   switch (head_dim) {
     case 40:
@@ -630,17 +652,15 @@ static int flash_attn_impl(a3d_stream_t stream, const void* Q, const void* K, co
       break;
     case 64: launch<64, 64, 1, OFS_FMA>(aligned, groups, s, p); break;        // CLIP text tower (12 heads of 64)
     case 160:
-#ifndef A3D_EXP_R5_PATHS      // (measurement build: the generic kernel as in rounds 1-5)
       // LDS-DMA staged kernel on eight waves (flash_attn_dm160.hip, round 6): 64-key tiles from 256 keys, both storage types
       // (16-byte stores: O and its row pitch must be 16-byte multiples — the entry point itself only asks for 8)
       // (no lower bound on q_len: the choice must depend on the KEY side only — a view-sharded rank sees a quarter of the queries against the same gathered
       // keys, 64 at level 3, and has to reproduce the unsharded launch bit for bit; a workgroup with few valid queries costs what any workgroup costs)
       if (!plain && !p.causal && kv_len % 64 == 0 && kv_len >= 256 && ((kmap->seg_len % 64 == 0) || (kv_len <= kmap->seg_len)) &&
-          (reinterpret_cast<uintptr_t>(O) & 15u) == 0 && omap->ld % 8 == 0) {
+          a3d_aligned(16, O) && omap->ld % 8 == 0) {
         if (int rc = A3D_FN(a3d_launch_flash_dm160)(exact ? 0 : 1, groups, s, p)) return rc;
         break;
       }
-#endif
       launch<160, 32, 1, OFS_FMA>(aligned, groups, s, p);
       break;
     default: return A3D_EUNSUPPORTED;
@@ -673,7 +693,7 @@ extern "C" int A3D_FN(a3d_flash_attn_counted)(a3d_stream_t stream, const void* Q
                                            const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* omap,
                                            int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len,
                                            float scale, float out_scale, int accumulate, unsigned int* counters) {
-  if (!counters || (reinterpret_cast<uintptr_t>(counters) & 3u)) return A3D_EINVAL;
+  if (!counters || !a3d_aligned(4, counters)) return A3D_EINVAL;
   return flash_attn_impl(stream, Q, K, V, O, qmap, kmap, omap, groups, heads, head_dim, q_len, kv_len, scale, out_scale, accumulate, nullptr, counters);
 }
 
@@ -684,22 +704,10 @@ extern "C" int A3D_FN(a3d_flash_attn2)(a3d_stream_t stream, const void* Q, const
                                     const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* kmap2, const a3d_rowmap* omap,
                                     int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len, int64_t kv_len2,
                                     float scale, float out_scale, float out_scale2, int accumulate) {
-  if (!Q || !K || !V || !K2 || !V2 || !O || groups <= 0 || heads <= 0 || q_len <= 0 || kv_len <= 0 || kv_len2 <= 0) return A3D_EINVAL;
-  if (!map_ok(qmap, head_dim) || !map_ok(kmap, head_dim) || !map_ok(kmap2, head_dim) || !map_ok(omap, head_dim)) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(K2) |
-       reinterpret_cast<uintptr_t>(V2)) & 15u) return A3D_EINVAL;
-  if (reinterpret_cast<uintptr_t>(O) & 7u) return A3D_EINVAL;
-  if (groups > 65535 || q_len > 0x3fffffffLL || kv_len > 0x3fffffffLL || kv_len2 > 0x3fffffffLL || kmap->seg_len > 0x3fffffffLL ||
-      kmap2->seg_len > 0x3fffffffLL) return A3D_EINVAL;
-  if (head_dim != 40 && head_dim != 80) return A3D_EUNSUPPORTED;
-  AttnParams p{};
-  p.Q = (const uint16_t*)Q; p.K = (const uint16_t*)K; p.V = (const uint16_t*)V; p.O = (uint16_t*)O;
-  p.K2 = (const uint16_t*)K2; p.V2 = (const uint16_t*)V2;
-  p.qm = *qmap; p.km = *kmap; p.km2 = *kmap2; p.om = *omap;
-  p.heads = heads; p.q_len = (int)q_len; p.kv_len = (int)kv_len; p.kv_len2 = (int)kv_len2;
-  if (accumulate & ~(A3D_ATTN_ACCUMULATE | A3D_ATTN_PLAIN)) return A3D_EINVAL;
-  p.scale_log2 = scale * 1.4426950408889634f; p.out_scale = out_scale; p.out_scale2 = out_scale2; p.accumulate = accumulate & 1; p.causal = 0;
-  const bool aligned = ((kmap->seg_len % 64 == 0) || (kv_len <= kmap->seg_len)) && ((kmap2->seg_len % 64 == 0) || (kv_len2 <= kmap2->seg_len));
+  AttnParams p;
+  bool aligned;
+  if (int rc = attn_args(true, Q, K, V, K2, V2, O, qmap, kmap, kmap2, omap, groups, heads, head_dim, q_len, kv_len, kv_len2,
+                         scale, out_scale, out_scale2, accumulate, A3D_ATTN_ACCUMULATE | A3D_ATTN_PLAIN, p, aligned)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (head_dim == 40 && !(accumulate & A3D_ATTN_PLAIN)) {      // level 0: the register-resident cross-attention kernel (cross_attn.hip)
     const int rc = A3D_FN(a3d_launch_cross_attn40)(groups, s, p);

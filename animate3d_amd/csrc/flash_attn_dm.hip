@@ -340,16 +340,6 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
         p.lse[((int64_t)grp * p.heads + head) * p.q_len + q_idx] = __builtin_amdgcn_logf(l_row[i]) - noff;
     }
   };
-  auto store4 = [&](uint16_t* dst, float v0, float v1, float v2, float v3) __attribute__((always_inline)) {
-    if (p.accumulate) {
-      const u32x2_t prev = *reinterpret_cast<const u32x2_t*>(dst);
-      v0 += lo16(prev[0]); v1 += hi16(prev[0]); v2 += lo16(prev[1]); v3 += hi16(prev[1]);
-    }
-    u32x2_t o;
-    o[0] = pack16(v0, v1);
-    o[1] = pack16(v2, v3);
-    *reinterpret_cast<u32x2_t*>(dst) = o;
-  };
   auto store_out = [&](const float (&inv)[NINV]) __attribute__((always_inline)) {
     if constexpr (PV16) {      // lane holds O[q = 16 nb + i16][d = 16 mb + 4 q4 + r]
 #pragma unroll
@@ -360,7 +350,7 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
 #pragma unroll
           for (int mb = 0; mb < 3; ++mb) {
             const int d = 16 * mb + 4 * q4;
-            if (d < D) store4(orow + d, oacc16[mb][nb][0] * inv[nb], oacc16[mb][nb][1] * inv[nb], oacc16[mb][nb][2] * inv[nb], oacc16[mb][nb][3] * inv[nb]);
+            if (d < D) store4(orow + d, p.accumulate, oacc16[mb][nb][0] * inv[nb], oacc16[mb][nb][1] * inv[nb], oacc16[mb][nb][2] * inv[nb], oacc16[mb][nb][3] * inv[nb]);
           }
         }
       }
@@ -370,13 +360,7 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
         const int q_idx = qt * BQ + wid * 32 * QT + qs * 32 + l31;
         if (q_idx < p.q_len) {
           uint16_t* orow = p.O + map_row(p.om, grp, q_idx) * p.om.ld + hoff;
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-              const int d = 32 * mt + 8 * qd + 4 * g;
-              if (d < D) store4(orow + d, oacc[qs][mt][4 * qd] * inv[qs], oacc[qs][mt][4 * qd + 1] * inv[qs], oacc[qs][mt][4 * qd + 2] * inv[qs], oacc[qs][mt][4 * qd + 3] * inv[qs]);
-            }
+          store_acc8<D, MT>(orow, g, p.accumulate, [&](int mt, int r) __attribute__((always_inline)) { return oacc[qs][mt][r] * inv[qs]; });
         }
       }
     }

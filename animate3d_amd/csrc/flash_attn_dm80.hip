@@ -42,12 +42,6 @@ constexpr float E_BIAS = 40.f;
 constexpr bool E_SAMPLED = false;
 #endif
 
-#ifdef A3D_EXP_R5_PATHS
-constexpr bool E_EARLY_DMA = false;      // measurement build: round 5's prologue order (Q rows first) and 8-byte stores, for the same-box A/B
-#else
-constexpr bool E_EARLY_DMA = true;
-#endif
-
 extern __shared__ __attribute__((aligned(16))) uint8_t e_smem[];
 A3D_DEV u32x4_t e_lds128(uint32_t off) { return *reinterpret_cast<const u32x4_t*>(e_smem + off); }
 A3D_DEV u32x2_t e_ldstr(uint32_t off) { return lds_tr16_b64(reinterpret_cast<const uint16_t*>(e_smem + off)); }
@@ -143,7 +137,7 @@ __global__ __launch_bounds__(512, 2) void flash_attn_dm80_kernel(const AttnParam
     dma_a(2); dma_b(2); dma_c(2);
   };
   auto prologue_wait = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "i"(NDMA) : "memory"); };
-  if constexpr (E_EARLY_DMA) prologue_issue();
+  prologue_issue();
 
   // ---- Q^T fragments (pre-scaled by scale * log2 e)
   const int q_idx = qt * BQ + wid * 32 + l31;
@@ -230,7 +224,7 @@ __global__ __launch_bounds__(512, 2) void flash_attn_dm80_kernel(const AttnParam
       p.lse[((int64_t)grp * p.heads + head) * p.q_len + q_idx] = __builtin_amdgcn_logf(l_tot) - minit[0];
     if (q_idx < p.q_len) {      // lane holds O[q = l31][d = 32*mt + 8*qd + 4*g + j]
       uint16_t* orow = p.O + map_row(p.om, grp, q_idx) * p.om.ld + hoff;
-      const bool wide_rows = E_EARLY_DMA && !p.accumulate && ((reinterpret_cast<uintptr_t>(p.O) | (uintptr_t)(p.om.ld * 2)) & 15u) == 0;      // (workgroup-uniform)
+      const bool wide_rows = !p.accumulate && ((reinterpret_cast<uintptr_t>(p.O) | (uintptr_t)(p.om.ld * 2)) & 15u) == 0;      // (workgroup-uniform)
       if (wide_rows) {
         // round 6: the two halves of a wave hold alternate 4-dim groups of one row; one v_permlane32_swap per packed word hands each half 8
         // CONSECUTIVE dims of two groups: five 16-byte stores per lane instead of ten 8-byte ones (the store tail is issue-bound)
@@ -331,7 +325,6 @@ __global__ __launch_bounds__(512, 2) void flash_attn_dm80_kernel(const AttnParam
       }
     };
 
-    if constexpr (!E_EARLY_DMA) prologue_issue();
     prologue_wait();
     {
       float m_off;
@@ -393,7 +386,7 @@ __global__ __launch_bounds__(512, 2) void flash_attn_dm80_kernel(const AttnParam
     clear_o();
     float m_off;
     f32x16_t sc;
-    if constexpr (decltype(rerun_c)::value || !E_EARLY_DMA) prologue_issue();      // (every wave has left the LDS images: the vote / the row-sum check were barriers)
+    if constexpr (decltype(rerun_c)::value) prologue_issue();      // (every wave has left the LDS images: the vote / the row-sum check were barriers)
     prologue_wait();
     first_scores(sc, m_off, 0.f);
     for (int t = 0; t < nt; ++t) {

@@ -1,5 +1,6 @@
-// Shared pieces of the flash-attention translation units (flash_attn.hip: plain / ping-pong / interleaved kernels and the
-// C-ABI entry point; flash_attn_dm.hip: the LDS-DMA staged level-0 kernel).
+// Shared pieces of the attention translation units: flash_attn.hip (generic kernels and the forward C-ABI entry points),
+// flash_attn_dm.hip / flash_attn_dm80.hip / flash_attn_dm160.hip (the LDS-DMA staged kernels of head_dim 40 / 80 / 160), cross_attn.hip
+// (two short key sets, head_dim 40) and attn_bwd.hip (the backward).  Device helpers only: no __global__ function is defined here.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -90,14 +91,18 @@ A3D_DEV void dm_glds16_q(uint32_t voff, const void* sbase, uint32_t lds_dst) {
                "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
                : "=&s"(keep), "=&s"(ex) : "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
 }
-// the same under a wave-uniform lane mask (0 = this wave has no share of the tile)
-A3D_DEV void dm_glds16_m(uint32_t voff, const void* sbase, uint32_t lds_dst, uint64_t mask) {
+// the same under a wave-uniform lane mask (0 = this wave has no share of the tile) that is in scalar registers already
+A3D_DEV void dm_glds16_sm(uint32_t voff, const void* sbase, uint32_t lds_dst, uint64_t mask) {
   unsigned keep;
   uint64_t ex;
-  mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mask >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)mask);
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_mov_b64 %1, exec\n\ts_mov_b64 exec, %5\n\ts_nop 0\n\t"
                "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
                : "=&s"(keep), "=&s"(ex) : "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_dst)), "s"(mask) : "memory");
+}
+// ... and for a mask the compiler does not know to be wave-uniform: say so
+A3D_DEV void dm_glds16_m(uint32_t voff, const void* sbase, uint32_t lds_dst, uint64_t mask) {
+  mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mask >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)mask);
+  dm_glds16_sm(voff, sbase, lds_dst, mask);
 }
 A3D_DEV const uint16_t* dm_scalar(const uint16_t* ptr) {      // wave-uniform by construction; say so
   const uint64_t a = (uint64_t)(uintptr_t)ptr;
@@ -107,11 +112,33 @@ A3D_DEV const uint16_t* dm_scalar(const uint16_t* ptr) {      // wave-uniform by
 
 // one thread of the workgroup books an event of the diagnostics counters (cold paths only)
 A3D_DEV void dm_count(const AttnParams& p, int which) {
-#ifndef A3D_EXP_R5_PATHS          // (measurement build: the round-5 kernels without the counters, for the same-box A/B of the level-0 launch)
   if (p.counters != nullptr && threadIdx.x == 0) atomicAdd(p.counters + which, 1u);
-#endif
 }
 
+// ---- output epilogue.  The 32x32 O^T accumulator tiles of a wave leave lane (l31, half g) with O[q = l31][d = 32 mt + 8 qd + 4 g + j] in
+// register 4 qd + j of tile mt; `orow` is the lane's row of O at its head, `val(mt, r)` the finished float of register r of tile mt.
+// four consecutive dims: 8 bytes at dst, added to what is there if `accumulate`
+A3D_DEV void store4(uint16_t* dst, bool accumulate, float v0, float v1, float v2, float v3) {
+  if (accumulate) {
+    const u32x2_t prev = *reinterpret_cast<const u32x2_t*>(dst);
+    v0 += lo16(prev[0]); v1 += hi16(prev[0]); v2 += lo16(prev[1]); v3 += hi16(prev[1]);
+  }
+  u32x2_t o;
+  o[0] = pack16(v0, v1);
+  o[1] = pack16(v2, v3);
+  *reinterpret_cast<u32x2_t*>(dst) = o;
+}
+// 8 bytes per access, in the accumulators' own layout
+template <int D, int MT, typename F>
+A3D_DEV void store_acc8(uint16_t* orow, int g, bool accumulate, F&& val) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int d = 32 * mt + 8 * qd + 4 * g;
+      if (d < D) store4(orow + d, accumulate, val(mt, 4 * qd), val(mt, 4 * qd + 1), val(mt, 4 * qd + 2), val(mt, 4 * qd + 3));
+    }
+}
 A3D_DEV uint32_t fa_lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }

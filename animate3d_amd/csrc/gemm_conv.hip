@@ -359,9 +359,7 @@ constexpr int PERSIST_MIN_FILL = 50;     // minimum average CU fill (per cent) o
 // a workspace, EPI_LINEAR, 16-bit output) must beat S = 1 by 15 % and leave >= 9 K-tiles per item, conv items hold whole 64-channel slices.
 struct PPPlan { int nb, S, cus; int64_t tiles_m, tiles_n; };
 constexpr int SPLITK_MAX = 16;
-#ifndef A3D_EXP_SPLITK_MINK
-#define A3D_EXP_SPLITK_MINK 9          // fewest K-tiles a split-K work item may hold (measurement builds override it)
-#endif
+constexpr int SPLITK_MINK = 9;          // fewest K-tiles a split-K work item may hold
 template <int CONV, int EPI>
 bool plan_persist(const GemmParams& p, int flags, bool allow_split, PPPlan& out) {
   if (a3d_gemm_kernel_of(flags) == A3D_GEMM_TILE128 || p.out_f32) return false;
@@ -396,7 +394,7 @@ bool plan_persist(const GemmParams& p, int flags, bool allow_split, PPPlan& out)
     if (p.N % (nb * 64) != 0) continue;
     const int64_t tiles = tm * (p.N / (nb * 64));
     for (int S = 1; S <= (allow_split && EPI == EPI_LINEAR ? SPLITK_MAX : 1); ++S) {
-      if ((nk / unit) % S != 0 || (S > 1 && nk / S < A3D_EXP_SPLITK_MINK)) continue;
+      if ((nk / unit) % S != 0 || (S > 1 && nk / S < SPLITK_MINK)) continue;
       const int64_t items = tiles * S;
       const int64_t rounds = (items + cus_plan - 1) / cus_plan;
       if (items * 100 < rounds * cus_plan * PERSIST_MIN_FILL) continue;             // average fill of the rounds (per cent)

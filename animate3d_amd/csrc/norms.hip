@@ -279,9 +279,6 @@ __global__ __launch_bounds__(512) void gn_fused_kernel(const GNParams p, const i
 // slab / thread plan of gn_fused_kernel; false: the instance does not fit (three-launch path)
 struct GNFPlan { int sg, nx, ny, threads, nslab, iters; };
 inline bool gn_fused_plan(int64_t rows, int C, int groups, GNFPlan& out) {
-#ifdef A3D_EXP_R5_PATHS
-  return false;          // measurement build (tools/microbench.py, A3D_LIB=...): the round-5 three-launch GroupNorm for every instance
-#endif
   const int cg = C / groups;
   int best_sg = 0;
   for (int sg = 1; sg <= groups; ++sg) {                 // widest slab (<= 640 bytes per row) that fits the registers of 512 threads

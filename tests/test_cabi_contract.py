@@ -11,6 +11,7 @@ import pytest
 from animate3d_amd.hip_ops import RowMap
 
 A3D_EINVAL = -1
+A3D_EUNSUPPORTED = -2
 BASE = 0x7F00_0010_0000          # fake device addresses: BASE + 0x10_0000 * i, 256-byte aligned
 
 
@@ -85,3 +86,68 @@ def test_flash_attn_bwd_refuses_do_scale_without_reciprocal(lib, do_scale, f16):
     fn = getattr(lib, _twin("a3d_flash_attn_bwd_bf16", f16))
     for accumulate in (0, 1, 3):
         assert fn(*_flash_attn_bwd(_ptrs(CASES["a3d_flash_attn_bwd_bf16"][0]), do_scale, accumulate)) == A3D_EINVAL
+
+
+# ---- forward attention (a3d_flash_attn, _lse, _counted, a3d_flash_attn2): one argument check serves the four entry points
+ACCUMULATE, CAUSAL, EXACT, PLAIN = 1, 2, 4, 8          # A3D_ATTN_* of include/animate3d_hip.h
+FWD_OPERANDS = {"a3d_flash_attn_bf16": ("Q", "K", "V", "O"), "a3d_flash_attn_lse_bf16": ("Q", "K", "V", "O", "lse2"),
+                "a3d_flash_attn_counted_bf16": ("Q", "K", "V", "O", "counters"), "a3d_flash_attn2_bf16": ("Q", "K", "V", "K2", "V2", "O")}
+FWD_VALID = dict(groups=4, heads=8, head_dim=40, q_len=64, kv_len=64, kv_len2=64, flags=0, ld=dict(q=320, k=320, k2=320, o=320))
+
+
+def _fwd_call(lib, entry, f16, ptr=None, ld=None, **geometry):
+    """The valid launch of `entry` (head_dim 40, 64 queries, 64 keys, 4 groups of 8 heads) with the named pointers / row pitches /
+    geometry words replaced.  Callers replace exactly one, and never none."""
+    assert ptr or ld or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(FWD_OPERANDS[entry])
+    p.update(ptr or {})
+    g = dict(FWD_VALID, **geometry)
+    lds = dict(FWD_VALID["ld"], **(ld or {}))
+    shape = [g["groups"], g["heads"], g["head_dim"], g["q_len"], g["kv_len"]]
+    if entry == "a3d_flash_attn2_bf16":
+        args = [None, p["Q"], p["K"], p["V"], p["K2"], p["V2"], p["O"], _map(lds["q"]), _map(lds["k"]), _map(lds["k2"]), _map(lds["o"]),
+                *shape, g["kv_len2"], 40 ** -0.5, 1.0, 0.5, g["flags"]]
+    else:
+        args = [None, p["Q"], p["K"], p["V"], p["O"], _map(lds["q"]), _map(lds["k"]), _map(lds["o"]), *shape, 40 ** -0.5, 1.0, g["flags"]]
+        args += [p[n] for n in ("lse2", "counters") if n in p]
+    return getattr(lib, _twin(entry, f16))(*args)
+
+
+FWD = pytest.mark.parametrize("entry", sorted(FWD_OPERANDS))
+F16 = pytest.mark.parametrize("f16", [False, True], ids=["bf16", "fp16"])
+
+
+@F16
+@FWD
+def test_flash_attn_refuses_misaligned_or_missing_operand(lib, entry, f16):
+    """Q, K, V (K2, V2) are read 16 bytes at a time, O is written 8 bytes at a time, the counters are 4-byte words; lse2 and the counters
+    are what their entry points exist for, so NULL is refused there."""
+    base = _ptrs(FWD_OPERANDS[entry])
+    for operand in FWD_OPERANDS[entry]:
+        off = {"O": 4, "counters": 2, "lse2": None}.get(operand, 8)
+        if off is not None:
+            rc = _fwd_call(lib, entry, f16, ptr={operand: base[operand] + off})
+            assert rc == A3D_EINVAL, f"{entry}: {operand} at +{off} bytes returned {rc}"
+        if operand in ("lse2", "counters"):
+            rc = _fwd_call(lib, entry, f16, ptr={operand: None})
+            assert rc == A3D_EINVAL, f"{entry}: NULL {operand} returned {rc}"
+
+
+@F16
+@FWD
+def test_flash_attn_refuses_bad_geometry(lib, entry, f16):
+    """Flag bits outside the entry point's set, more groups than a grid's y extent, sequence positions beyond the 32-bit row maps'
+    range and row pitches that break the 16-byte rows are A3D_EINVAL; shapes without a kernel are A3D_EUNSUPPORTED."""
+    two = entry == "a3d_flash_attn2_bf16"
+    for flags in ([CAUSAL, EXACT, 16, ACCUMULATE | 32] if two else [16, ACCUMULATE | 32]):
+        assert _fwd_call(lib, entry, f16, flags=flags) == A3D_EINVAL, f"{entry}: flags {flags}"
+    assert _fwd_call(lib, entry, f16, groups=65536) == A3D_EINVAL
+    for length in ("q_len", "kv_len") + (("kv_len2",) if two else ()):
+        assert _fwd_call(lib, entry, f16, **{length: 2 ** 30}) == A3D_EINVAL, f"{entry}: {length} = 2^30"
+    for which in ("q", "k", "o") + (("k2",) if two else ()):
+        assert _fwd_call(lib, entry, f16, ld={which: 324}) == A3D_EINVAL, f"{entry}: ld of the {which} map = 324"
+    assert _fwd_call(lib, entry, f16, head_dim=48) == A3D_EUNSUPPORTED
+    if two:
+        assert _fwd_call(lib, entry, f16, head_dim=160) == A3D_EUNSUPPORTED
+    else:
+        assert _fwd_call(lib, entry, f16, flags=CAUSAL) == A3D_EUNSUPPORTED          # head_dim 40: causal is offered at 64 / 160 only

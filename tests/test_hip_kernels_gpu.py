@@ -495,6 +495,61 @@ def test_flash_attn_kernel_variants_agree(ops, ref):
         check(f"D40 kernel choice {mode}", ops.flash_attn(q, k, v, qm, k0, b * F, heads, n * L, n * L, **kw), want)
 
 
+@pytest.fixture(scope="module")
+def store_cases(ref):
+    """Inputs and fp32 references of test_flash_attn_output_stores per (head_dim, storage type), computed once and shared by the modes."""
+    cases = {}
+
+    def get(D, dtype):
+        if (D, dtype) not in cases:
+            heads, q_len, L = 2, 300, 512
+            C = heads * D
+            q, k, v = rnd(q_len, C, seed=D, dtype=dtype), rnd(L, C, seed=D + 1, dtype=dtype), rnd(L, C, seed=D + 2, dtype=dtype)
+            base = rnd(q_len, C, seed=D + 3, dtype=dtype)
+            qm, km = RowMap(1, q_len, 0, q_len, 0), RowMap(1, L, 0, L, 0)
+            fresh = ref.flash_attn(q, k, v, qm, km, 1, heads, q_len, L)
+            summed = ref.flash_attn(q, k, v, qm, km, 1, heads, q_len, L, out=base.float(), out_scale=0.6, accumulate=True)
+            cases[(D, dtype)] = (q, k, v, base, fresh, summed)
+        return cases[(D, dtype)]
+    return get
+
+
+@pytest.mark.parametrize("mode", sorted(ATTN_MODES))
+@pytest.mark.parametrize("storage", ["bf16", "fp16"])
+@pytest.mark.parametrize("D", [40, 80, 160])
+def test_flash_attn_output_stores(request, store_cases, D, storage, mode):
+    """Every way an attention kernel writes O, at the smallest shape that reaches each LDS-DMA staged kernel (512 keys) with a ragged
+    last workgroup (300 queries, 2 heads): a fresh output, accumulation into an aligned one, and both into a column view whose base is
+    8 bytes off a 16-byte boundary while its row pitch is a 16-byte multiple — the 8-byte stores of the head_dim-80 staged kernel, and
+    at head_dim 160 the generic kernel the dispatcher falls back to.  The four columns on either side of the view must keep their
+    contents.  Bars: 4e-3, 6e-3 where the previous O is added."""
+    a = request.getfixturevalue("ops" if storage == "bf16" else "ops16")
+    dtype = BF if storage == "bf16" else H16
+    heads, q_len, L, sentinel = 2, 300, 512, 7.0
+    C = heads * D
+    q, k, v, base, fresh, summed = store_cases(D, dtype)
+    qm, km = RowMap(1, q_len, 0, q_len, 0), RowMap(1, L, 0, L, 0)
+    kw = ATTN_MODES[mode]
+    name = f"attn stores D{D} {storage} {mode}"
+
+    def into_view(fill, **call):
+        buf = torch.full((q_len, C + 8), sentinel, device="cuda", dtype=dtype)
+        view = buf[:, 4:4 + C]
+        if fill is not None:
+            view.copy_(fill)
+        assert view.data_ptr() % 16 == 8 and (view.stride(0) * 2) % 16 == 0
+        a.flash_attn(q, k, v, qm, km, 1, heads, q_len, L, out=view, **call, **kw)
+        assert (buf[:, :4] == sentinel).all() and (buf[:, 4 + C:] == sentinel).all(), f"{name}: wrote outside the view"
+        return view
+
+    check(f"{name} fresh", a.flash_attn(q, k, v, qm, km, 1, heads, q_len, L, **kw), fresh)
+    check(f"{name} view", into_view(None), fresh)
+    o = base.clone()
+    a.flash_attn(q, k, v, qm, km, 1, heads, q_len, L, out=o, out_scale=0.6, accumulate=True, **kw)
+    check(f"{name} accumulate", o, summed, tol=6e-3)
+    check(f"{name} accumulate view", into_view(base, out_scale=0.6, accumulate=True), summed, tol=6e-3)
+
+
 @pytest.mark.parametrize("D", [40, 80, 160])
 @pytest.mark.parametrize("V,F,L", [(2, 3, 16), (1, 4, 64), (2, 16, 64), (1, 32, 8), (1, 3, 5), (3, 16, 7)])
 def test_temporal_attn(ops, ref, D, V, F, L):

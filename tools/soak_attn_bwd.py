@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Race / miscount detector for the LDS-DMA staged attention backward (csrc/attn_bwd.hip, round 6): seeded cases at every head dim and both
 key maps, repeated under unrelated HBM traffic; prints one sha256 per (case, repeat) of dQ | dK | dV.  Run once with the in-tree library and
-once with a side build that keeps the register staging (python -m animate3d_amd.build --experiment A3D_EXP_BWD_NODMA; A3D_LIB=...): the two
-stagings move the same bytes into the same LDS image, so every line must be identical."""
+once with a library that keeps the register staging (A3D_LIB=...): the two stagings move the same bytes into the same LDS image, so every
+line must be identical.  The kernel's compile-time switch for such a build is gone from the tree; commit ed44278 is the last one that has
+it (see the launch function of csrc/attn_bwd.hip there, and python -m animate3d_amd.build --experiment)."""
 import hashlib
 import os
 import sys
