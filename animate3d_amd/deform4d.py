@@ -8,7 +8,8 @@ gaussian_batch_renderer_4d.py:27-60.  ``deform_gaussians`` / ``HexPlaneDeformati
 Contract (all arithmetic fp32)
 
 Inputs: ``xyz [N, 3]``, ``scaling [N, 3]`` (log-scale), ``rotation [N, 4]`` (r, x, y, z, un-normalised), ``timestamps [T]`` in [-1, 1],
-optional ``image_to_time [B]`` (int64 index into ``timestamps``; default identity, B = T).
+optional ``image_to_time [B]`` (int64 or int32 index into ``timestamps``; default identity, B = T).  Any view is accepted: what is not
+contiguous, or (``rotation``, the ``rotations`` cotangent) does not start on the 16 bytes the kernels read at a time, is copied first.
 Parameters: ``grids[s][p]`` of shape ``[1, C, reso[b], reso[a]]`` for the plane over coordinates ``(a, b)`` in
 ``itertools.combinations(range(4), 2)`` order (the axis order is reversed, gaussian_4d.py:162-167); ``delta_xyz_network``,
 ``delta_rot_network``, ``delta_scaling_network`` and, with ``use_global_trans``, ``global_rot_network``, ``global_trans_network``: each
@@ -136,9 +137,16 @@ def _pack_weights(nets: Dict[str, Sequence[torch.Tensor]], device) -> torch.Tens
     return w
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` (contiguous) where the kernels may read it 16 bytes at a time: itself, or a copy when it is a view that starts elsewhere (a
+    parameter inside a flat buffer, behind a number of floats that is no multiple of four)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _DeformGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, rotation, xyz, timestamps, image_to_time, grid_size, flags, plan, net_names, *params):
+        ctx.set_materialize_grads(False)                         # an output outside the loss arrives in backward as None, not as zeros
         lib, dev = load_library(), xyz.device
         N, T = xyz.shape[0], timestamps.shape[0]
         grids, weights = params[:12], params[12:]
@@ -151,7 +159,8 @@ class _DeformGaussians(torch.autograd.Function):
         img_list = torch.argsort(i2t, stable=True).to(torch.int32)
         img_start = torch.zeros(T + 1, dtype=torch.int32, device=dev)
         img_start[1:] = torch.cumsum(torch.bincount(i2t, minlength=T), 0)
-        x, sc, ro, ts = xyz.detach().contiguous(), scaling.detach().contiguous(), rotation.detach().contiguous(), timestamps.detach().contiguous()
+        x, sc, ts = xyz.detach().contiguous(), scaling.detach().contiguous(), timestamps.detach().contiguous()
+        ro = _aligned16(rotation.detach().contiguous())
         f32 = dict(dtype=torch.float32, device=dev)
         sp = torch.empty(N, 32, **f32)
         gmean = glob = mpart = None
@@ -173,6 +182,7 @@ class _DeformGaussians(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         desc, _, _ = _plane_desc(grid_size)
         cot = [torch.zeros(B, N, k, **f32) if g is None else g.float().contiguous() for g, k in ((d_means, 3), (d_scales, 3), (d_rots, 4))]
+        cot[2] = _aligned16(cot[2])
         ws = torch.empty(int(lib.a3d_dg_backward_ws_floats(T, N, desc)), **f32)
         d_grid, d_w = torch.empty(total, **f32), torch.empty(5, NET_FLOATS, **f32)
         d_scaling, d_rotation = torch.empty(N, 3, **f32), torch.empty(N, 4, **f32)

@@ -22,9 +22,52 @@ SCENES = {
 }
 
 
+NONCUBIC = ((6, 5, 7, 3), (12, 10, 14, 6))                 # W != H in every plane, both scales (the golden scene's grid)
+# twelve points of the ``lattice`` scene, dyadic on its grid (every resolution - 1 a power of two): corners, texel lattice points where
+# w1 == 0 exactly, points clamped at the border on some or all axes, and cell interiors next to them
+LATTICE_POINTS = ((-1, -1, -1), (1, 1, 1), (1, -1, 0), (0, 0, 0), (-.5, .5, .25), (3, -3, .5),
+                  (-2.5, .75, 4), (.5, 0, -.75), (1, .3, -.2), (.1, -1, .9), (.25, .5, -.5), (-.75, -.5, .125))
+
+
+def _edge(N, grid_size, timestamps, seed, image_to_time=None, fixed=None, spread=0.7, center=None, branches=True, outside=True):
+    """One row of EDGE_SCENES.  ``branches`` / ``outside``: whether the scene is large and wide enough that all four quaternion branches
+    occur and that some point lies outside [-1, 1]."""
+    return dict(N=N, grid_size=grid_size, timestamps=timestamps, seed=seed, image_to_time=image_to_time, fixed=fixed, spread=spread,
+                center=center, branches=branches, outside=outside)
+
+
+# the scenes of tests/test_deform4d_edges_gpu.py; with SCENES, every scene a deform4d test compares on.  Sizes are the smallest at which
+# each seam exists: 256 Gaussians per forward block, 128-row tiles and 512-row slabs in the backward, 4 / 16 slices in the gathers.
+EDGE_SCENES = {
+    "noncubic": _edge(129, NONCUBIC, (-1.0, -0.4, 0.3, 1.0), 7, image_to_time=(3, 0, 1, 1, 2, 0)),
+    "lattice": _edge(129, ((5, 3, 9, 3), (9, 5, 17, 5)), (-1.0, -0.5, 0.0, 0.5, 1.0, 0.3), 19, fixed=LATTICE_POINTS),    # seed: no planted point unsafe
+    "min_res": _edge(513, ((2, 2, 2, 2), (3, 2, 4, 2)), (-1.0, 0.0, 1.0, 0.4), 11),           # one cell per axis: gather lists of length N
+    "seam_1": _edge(1, NONCUBIC, (0.3, -0.6), 7, branches=False, outside=False),              # the mean over one Gaussian
+    "seam_128": _edge(128, NONCUBIC, (0.3, -0.6), 7),
+    "seam_129": _edge(129, NONCUBIC, (0.3, -0.6), 7),
+    "seam_512": _edge(512, NONCUBIC, (0.3, -0.6), 7),
+    "seam_513": _edge(513, NONCUBIC, (0.3, -0.6), 7),
+    # a few cells hold every Gaussian; every other texel's gradient is exactly zero
+    "cluster": _edge(600, RELEASED, (0.2, -0.7), 11, spread=0.004, center=(0.313, -0.207, 0.111), outside=False),
+    # frame and image bookkeeping, on the non-cubic grid
+    "one_frame": _edge(129, NONCUBIC, (0.3,), 7),
+    "first_frame_only": _edge(129, NONCUBIC, (-1.0, -1.0), 7),
+    "duplicate_frames": _edge(129, NONCUBIC, (0.3, 0.3, -1.0, -1.0), 7),
+    "unshown_frames": _edge(129, NONCUBIC, (0.35, -1.0, -0.62, 1.0, 0.05), 7, image_to_time=(4, 0, 0)),
+}
+
+
 def named_scene(name, use_global_trans=True):
-    N, grid_size, ts, seed = SCENES[name]
-    return make_scene(N, grid_size, ts, seed, use_global_trans=use_global_trans)
+    """The scene ``name`` of SCENES or EDGE_SCENES.  An edge scene carries its ``image_to_time`` (a tuple or None) as well."""
+    if name in SCENES:
+        N, grid_size, ts, seed = SCENES[name]
+        return make_scene(N, grid_size, ts, seed, use_global_trans=use_global_trans)
+    e = EDGE_SCENES[name]
+    fixed = None if e["fixed"] is None else torch.tensor(e["fixed"], dtype=torch.float32)
+    scene = make_scene(e["N"], e["grid_size"], e["timestamps"], e["seed"], use_global_trans=use_global_trans,
+                       spread=e["spread"], center=e["center"], fixed=fixed)
+    scene["image_to_time"] = e["image_to_time"]
+    return scene
 
 
 def cell_ids(xyz: torch.Tensor, grid_size) -> torch.Tensor:
@@ -166,11 +209,13 @@ def _unsafe(scene, use_global_trans, relu_margin=1e-5, branch_margin=1e-3):
     return bad, global_bad
 
 
-def make_scene(N, grid_size, timestamps, seed, use_global_trans=True, spread=0.7):
+def make_scene(N, grid_size, timestamps, seed, use_global_trans=True, spread=0.7, center=None, fixed=None):
     """Seeded inputs and parameters (float32, CPU).  Gaussians are resampled, not masked, until none has, in any frame and network, a
     hidden pre-activation below 1e-5 of that layer's RMS (a ReLU unit within fp32 rounding of zero switches a whole gradient term), nor a
     trace / diagonal difference of R build_rotation(q) within 1e-3 of a branch threshold of the quaternion extraction (whose sign flips
-    between branches).  ``spread`` > 0.5 puts some points outside [-1, 1]: the border clamp."""
+    between branches).  ``spread`` > 0.5 puts some points outside [-1, 1]: the border clamp; ``center`` moves the cloud.  ``fixed`` [K, 3]
+    is planted in the first K rows of ``xyz`` before the resampling (the global mean the other Gaussians are judged with includes it) and
+    never moves: a planted point that is itself unsafe is an error, answered with another seed."""
     g = torch.Generator().manual_seed(seed)
     grids = []
     for reso in grid_size:
@@ -183,14 +228,24 @@ def make_scene(N, grid_size, timestamps, seed, use_global_trans=True, spread=0.7
     nets = {n: (torch.randn(32, 32, generator=g) * 0.4, torch.randn(OUT[n], 32, generator=g) * 0.15) for n in names}
     scene = dict(xyz=torch.randn(N, 3, generator=g) * spread, scaling=torch.rand(N, 3, generator=g) * 2 - 4,
                  rotation=torch.randn(N, 4, generator=g), timestamps=torch.as_tensor(timestamps, dtype=torch.float32), grids=grids, nets=nets)
+    shift = None if center is None else torch.tensor(center, dtype=torch.float32)
+    if shift is not None:
+        scene["xyz"] += shift
+    K = 0 if fixed is None else fixed.shape[0]
+    if K:
+        assert K <= N and fixed.shape == (K, 3)
+        scene["xyz"][:K] = fixed
     for _ in range(50):
         bad, global_bad = _unsafe(scene, use_global_trans)
         assert not global_bad, "a global-network pre-activation sits at zero: pick another seed"
+        assert not bool(bad[:K].any()), "a planted point sits at a ReLU switch or a branch threshold: pick another seed"
         k = int(bad.sum())
         if k == 0:
             scene["resampled"] = _
             return scene
         scene["xyz"][bad] = torch.randn(k, 3, generator=g) * spread
+        if shift is not None:
+            scene["xyz"][bad] += shift
         scene["rotation"][bad] = torch.randn(k, 4, generator=g)
     raise AssertionError("resampling did not converge")
 

@@ -2,7 +2,8 @@
 the widest access the kernels make through it, or an attention-backward do_scale without a usable reciprocal, is refused with
 A3D_EINVAL before anything reaches the GPU.  The device addresses below are made up and never dereferenced: every call differs from a
 valid launch in exactly one operand, and the argument checks run before the first HIP call, so this runs on a machine without a GPU.
-(No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)"""
+(No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)  The forward attention entry
+points and the deformation field's (a3d_dg_*) are held to the same discipline further down."""
 import ctypes
 import math
 
@@ -151,3 +152,91 @@ def test_flash_attn_refuses_bad_geometry(lib, entry, f16):
         assert _fwd_call(lib, entry, f16, head_dim=160) == A3D_EUNSUPPORTED
     else:
         assert _fwd_call(lib, entry, f16, flags=CAUSAL) == A3D_EUNSUPPORTED          # head_dim 40: causal is offered at 64 / 160 only
+
+
+# ---- deformation field (a3d_dg_*, csrc/deform4d.hip): fp32 only, one build
+DG_T, DG_N, DG_B, DG_FLAGS = 3, 300, 5, 3          # flags: use_global_trans | deform_scales, so mpart / gmean / glob are required
+DG_ALIGN16 = ("grid", "rotation", "sp", "rots", "ws", "d_grid", "d_rots", "d_rotation")       # read or written 16 bytes at a time
+DG_OPERANDS = {
+    "a3d_dg_cells_f32": ("xyz", "cells"),
+    "a3d_dg_forward_f32": ("xyz", "scaling", "rotation", "ts", "grid", "w", "img_start", "img_list", "sp", "mpart", "gmean", "glob", "means",
+                           "scales", "rots"),
+    "a3d_dg_backward_f32": ("xyz", "scaling", "rotation", "ts", "grid", "w", "img_start", "img_list", "sp", "gmean", "glob", "order", "starts",
+                            "d_means", "d_scales", "d_rots", "ws", "d_grid", "d_weights", "d_scaling", "d_rotation"),
+}
+DG_OPTIONAL = ("mpart", "gmean", "glob")             # may be NULL without use_global_trans only
+
+
+def _dg_desc(off=None, W=None, H=None):
+    """Host plane descriptor off[12] | W[12] | H[12] of the grid ((6, 5, 7, 3), (12, 10, 14, 6)), entries replaced per {plane: value}."""
+    from animate3d_amd import deform4d
+    desc, _, _ = deform4d._plane_desc(((6, 5, 7, 3), (12, 10, 14, 6)))
+    for base, repl in ((0, off), (12, W), (24, H)):
+        for k, v in (repl or {}).items():
+            desc[base + k] = v
+    return desc
+
+
+def _dg_call(lib, entry, ptr=None, desc="valid", **geometry):
+    """The valid launch of `entry` (T = 3, N = 300, B = 5, flags 3) with the named pointers / the descriptor / geometry words replaced.
+    Callers replace exactly one, and never none."""
+    assert ptr or not isinstance(desc, str) or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(DG_OPERANDS[entry])
+    p.update(ptr or {})
+    g = dict(dict(T=DG_T, N=DG_N, B=DG_B, flags=DG_FLAGS), **geometry)
+    d = _dg_desc() if isinstance(desc, str) else desc
+    if entry == "a3d_dg_cells_f32":
+        return lib.a3d_dg_cells_f32(None, g["N"], p["xyz"], d, p["cells"])
+    head = [None, g["T"], g["N"], g["B"], p["xyz"], p["scaling"], p["rotation"], p["ts"], p["grid"], d, p["w"], g["flags"], p["img_start"],
+            p["img_list"]]
+    return getattr(lib, entry)(*head, *[p[n] for n in DG_OPERANDS[entry][8:]])
+
+
+DG = pytest.mark.parametrize("entry", sorted(DG_OPERANDS))
+
+
+@DG
+def test_deform_field_refuses_misaligned_or_missing_operand(lib, entry):
+    """Every operand moved off the alignment the kernels need (8 bytes off for a 16-byte access, 2 for a 4-byte one), every operand
+    NULL; mpart / gmean / glob are required because use_global_trans is set."""
+    base = _ptrs(DG_OPERANDS[entry])
+    for operand in DG_OPERANDS[entry]:
+        off = 8 if operand in DG_ALIGN16 else 2
+        rc = _dg_call(lib, entry, ptr={operand: base[operand] + off})
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +{off} bytes returned {rc}"
+        rc = _dg_call(lib, entry, ptr={operand: None})
+        assert rc == A3D_EINVAL, f"{entry}: NULL {operand} returned {rc}"
+    if entry != "a3d_dg_cells_f32":
+        for operand in ("rotation", "rots" if "rots" in base else "d_rots"):       # a float-aligned view: what a flat parameter buffer gives
+            assert _dg_call(lib, entry, ptr={operand: base[operand] + 4}) == A3D_EINVAL, operand
+
+
+@DG
+def test_deform_field_refuses_bad_geometry(lib, entry):
+    """Empty or oversized extents (T is a grid's y extent; T N and B N index 4-wide rows in 32 bits) and plane descriptors that are
+    absent, below the minimum resolution 2, above 32768, or whose offset is negative or breaks the 64-byte texel lines."""
+    cells = entry == "a3d_dg_cells_f32"
+    limit = (2 ** 31 - 1) // 4
+    bad = [dict(N=0), dict(N=-1)]
+    if not cells:
+        bad += [dict(T=0), dict(T=-1), dict(B=0), dict(B=-1), dict(T=65536), dict(T=1, N=limit + 1), dict(T=2, N=limit // 2 + 1),
+                dict(B=1, N=limit // DG_T + 1), dict(T=1, N=limit // DG_B + 1)]       # the last two: T N alone, B N alone
+    for g in bad:
+        assert _dg_call(lib, entry, **g) == A3D_EINVAL, f"{entry}: {g}"
+    assert _dg_call(lib, entry, desc=None) == A3D_EINVAL, f"{entry}: NULL plane descriptor"
+    for k in (0, 5, 11):
+        for field, values in (("W", (1, 0, 32769)), ("H", (1, 32769)), ("off", (-16, 8, 17))):
+            for v in values:
+                assert _dg_call(lib, entry, desc=_dg_desc(**{field: {k: v}})) == A3D_EINVAL, f"{entry}: plane {k} {field} = {v}"
+
+
+def test_deform_field_size_queries(lib):
+    """a3d_dg_mean_partials: blocks of 256 Gaussians; a3d_dg_backward_ws_floats: 0 for whatever a3d_dg_backward_f32 would refuse."""
+    assert [lib.a3d_dg_mean_partials(n) for n in (-1, 0, 1, 256, 257)] == [0, 0, 1, 1, 2]
+    ws = lib.a3d_dg_backward_ws_floats
+    assert ws(DG_T, DG_N, _dg_desc()) > 0 and ws(1, 1, _dg_desc()) > 0
+    assert ws(2 * DG_T, DG_N, _dg_desc()) > ws(DG_T, DG_N, _dg_desc()) < ws(DG_T, 2 * DG_N, _dg_desc())
+    for args in ((0, DG_N, _dg_desc()), (-1, DG_N, _dg_desc()), (DG_T, 0, _dg_desc()), (DG_T, -1, _dg_desc()), (DG_T, DG_N, None),
+                 (DG_T, DG_N, _dg_desc(W={3: 1})), (DG_T, DG_N, _dg_desc(H={8: 32769})), (DG_T, DG_N, _dg_desc(off={1: 8})),
+                 (DG_T, DG_N, _dg_desc(off={1: -16}))):
+        assert ws(*args) == 0, args[:2]

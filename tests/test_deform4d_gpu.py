@@ -42,23 +42,44 @@ def _run_ref(scene, dtype, names, i2t, cots, **kw):
         t.requires_grad_(True)
     outs = deform_ref.deform(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], {n: s["nets"][n] for n in names},
                              image_to_time=i2t, **kw)
-    loss = sum((o * c.to(dtype)).sum() for o, c in zip(outs, cots))
+    loss = sum((o * c.to(dtype)).sum() for o, c in zip(outs, cots) if c is not None)     # None: the output is left out of the loss
     grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
     grads = {k: (torch.zeros_like(t) if g is None else g) for (k, t), g in zip(leaves.items(), grads)}
     return dict(zip(("means", "scales", "rotations"), outs)), grads
 
 
-def _run_hip(scene, names, i2t, cots, **kw):
+def _run_hip(scene, names, i2t, cots, make=None, after=None, **kw):
+    """``make(name, tensor)`` replaces xyz / scaling / rotation (by a view of equal values); ``after`` wraps the outputs before the loss."""
     s = deform_ref.cast(scene, torch.float32, "cuda")
+    if make is not None:
+        for k in ("xyz", "scaling", "rotation"):
+            s[k] = make(k, s[k])
     leaves = _leaves(s, names)
     for t in leaves.values():
         t.requires_grad_(True)
     outs = deform4d.deform_gaussians(s["xyz"], s["scaling"], s["rotation"], s["timestamps"], s["grids"], {n: s["nets"][n] for n in names},
                                      image_to_time=None if i2t is None else i2t.cuda(), **kw)
-    loss = sum((o * c.cuda()).sum() for o, c in zip(outs, cots))
+    loss = sum((o * c.cuda()).sum() for o, c in zip(outs if after is None else after(outs), cots) if c is not None)
     grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
     grads = {k: (torch.zeros_like(t) if g is None else g) for (k, t), g in zip(leaves.items(), grads)}
     return dict(zip(("means", "scales", "rotations"), outs)), grads
+
+
+def _assert_parity(tag, ref64, ref32, got):
+    """The acceptance rule of this file's docstring on (outputs, gradients) pairs of dicts; prints one line per tensor."""
+    failures = []
+    for kind, r64, r32, out in (("out", ref64[0], ref32[0], got[0]), ("grad", ref64[1], ref32[1], got[1])):
+        for k in r64:
+            if float(r64[k].detach().abs().max()) == 0.0:                 # no path to this tensor in this configuration: exactly zero
+                print(f"[deform4d {tag}] {kind} {k}: reference is zero")
+                assert float(out[k].detach().abs().max()) == 0.0, k
+                continue
+            e32, err = _rel(r32[k], r64[k]), _rel(out[k], r64[k])
+            bar = max(4 * e32, FLOOR)
+            print(f"[deform4d {tag}] {kind} {k}: e32 {e32:.3e} kernel {err:.3e} bar {bar:.3e}")
+            if not err <= bar:
+                failures.append((kind, k, e32, err, bar))
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("use_global", [False, True])
@@ -79,19 +100,7 @@ def test_forward_and_gradients_against_float64(use_global, deform_scales, fft):
     o32, g32 = _run_ref(scene, torch.float32, names, i2t, cots, **kw)
     oh, gh = _run_hip(scene, names, i2t, cots, **kw)
     torch.cuda.synchronize()
-    failures = []
-    for kind, r64, r32, got in (("out", o64, o32, oh), ("grad", g64, g32, gh)):
-        for k in r64:
-            if float(r64[k].detach().abs().max()) == 0.0:                 # no path to this tensor in this configuration: exactly zero
-                print(f"[deform4d g{int(use_global)} s{int(deform_scales)} f{int(fft)}] {kind} {k}: reference is zero")
-                assert float(got[k].detach().abs().max()) == 0.0, k
-                continue
-            e32, err = _rel(r32[k], r64[k]), _rel(got[k], r64[k])
-            bar = max(4 * e32, FLOOR)
-            print(f"[deform4d g{int(use_global)} s{int(deform_scales)} f{int(fft)}] {kind} {k}: e32 {e32:.3e} kernel {err:.3e} bar {bar:.3e}")
-            if not err <= bar:
-                failures.append((kind, k, e32, err, bar))
-    assert not failures, failures
+    _assert_parity(f"g{int(use_global)} s{int(deform_scales)} f{int(fft)}", (o64, g64), (o32, g32), (oh, gh))
 
 
 def test_cells_kernel_matches_definition():

@@ -119,11 +119,15 @@ def test_binning_plan_against_brute_force():
 
 
 @pytest.mark.parametrize("name,use_global", [("gpu_parity", False), ("gpu_parity", True), ("golden", False), ("golden", True),
-                                             ("gradcheck", True)])
+                                             ("gradcheck", True)] + [(n, g) for n in deform_ref.EDGE_SCENES for g in (False, True)])
 def test_scene_conditions_hold_in_both_precisions(golden, name, use_global):
-    """Every scene a deform4d test compares on (deform_ref.SCENES; the golden one as stored): float32 and float64 choose the same ReLU
-    pattern and the same quaternion branch everywhere, and all four branches occur (the five-Gaussian gradcheck scene is too small for
-    that; it is used with use_global_trans only and in float64 only)."""
+    """Every scene a deform4d test compares on (deform_ref.SCENES, the golden one as stored, and deform_ref.EDGE_SCENES): float32 and
+    float64 choose the same ReLU pattern and the same quaternion branch everywhere, and all four branches occur (the five-Gaussian
+    gradcheck scene is too small for that; it is used with use_global_trans only and in float64 only).  An edge scene says in its table
+    row whether it is large enough for all four branches and wide enough for a point outside [-1, 1]."""
+    edge = deform_ref.EDGE_SCENES.get(name)
+    want_branches = name != "gradcheck" if edge is None else edge["branches"]
+    want_outside = name != "gradcheck" if edge is None else edge["outside"]
     if name == "golden":
         scene = _golden_scene(golden)
         gen = deform_ref.named_scene("golden")                        # the generator's scene is the stored one
@@ -137,10 +141,17 @@ def test_scene_conditions_hold_in_both_precisions(golden, name, use_global):
         assert torch.equal(r32[net], r64[net]), net
     if use_global:
         assert torch.equal(b32, b64)
-        if name != "gradcheck":
+        if want_branches:
             assert sorted(b64.unique().tolist()) == [0, 1, 2, 3]
-    if name != "gradcheck":
+    if want_outside:
         assert bool((scene["xyz"].abs() > 1).any())
+    if edge is not None:
+        assert scene["xyz"].shape[0] == edge["N"] and torch.equal(scene["timestamps"], torch.tensor(edge["timestamps"]))
+        if edge["fixed"] is not None:                                  # planted before the resampling, and still there
+            fixed = torch.tensor(edge["fixed"], dtype=torch.float32)
+            assert torch.equal(scene["xyz"][:len(fixed)], fixed)
+        if edge["center"] is not None:
+            assert float((scene["xyz"] - torch.tensor(edge["center"])).abs().max()) < 6 * edge["spread"]
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"), reason="needs llvm-objdump")
