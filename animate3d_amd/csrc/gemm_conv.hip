@@ -350,8 +350,26 @@ __global__ __launch_bounds__(256, (BKT == 64 ? 2 : 3)) void gemm_kernel(const Ge
 // =====================================================================================================================
 // The big token matrices (levels 0-2 of the UNet: M = 32768 ... 524288, 97 % of the GEMM / conv FLOPs) take the persistent
 // 256 x (NB*64) kernel of gemm_pp.hip (one 512-thread workgroup per CU, LDS-DMA staged K-tiles, ping-pong main loop).
-// returns -1000 when the shape is not eligible (caller falls back to the 128x128 kernel)
 constexpr int PBM = 256;
+constexpr int NOT_ELIGIBLE = -1000;      // try_launch_persist: the shape is not the persistent kernel's (no A3D_* code, no hipError_t)
+
+// the flags word of every entry point of the family: no bit outside the two fields, and a kernel choice that names a kernel
+inline bool gemm_flags_ok(int flags) {
+  return !(flags & ~(A3D_GEMM_RESERVED_CUS_MASK | A3D_GEMM_KERNEL_MASK)) && a3d_gemm_kernel_of(flags) <= A3D_GEMM_RING;
+}
+
+// compute units of the current device, queried once per device; 0 when the query fails (not cached: the next call asks again)
+inline int device_cus() {
+  static int cus_of[64] = {0};
+  const int dev = a3d_current_device();
+  if (cus_of[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cus_of[dev] = n > 0 ? n : 256;
+  }
+  return cus_of[dev];
+}
+
 constexpr int PERSIST_MIN_FILL = 50;     // minimum average CU fill (per cent) of the persistent grid's rounds: at 50 % (level 3, 128 tiles)
                                          // it still ties or beats the 128x128 kernel by 3-10 % (profiles/README.md, round 1)
 // Tile width and split-K factor of a persistent launch.  Returns false when the shape is not the persistent kernel's.  Cost model of one
@@ -363,17 +381,12 @@ constexpr int SPLITK_MINK = 9;          // fewest K-tiles a split-K work item ma
 template <int CONV, int EPI>
 bool plan_persist(const GemmParams& p, int flags, bool allow_split, PPPlan& out) {
   if (a3d_gemm_kernel_of(flags) == A3D_GEMM_TILE128 || p.out_f32) return false;
-  static int cus_of[64] = {0};
-  const int dev = a3d_current_device();
-  if (cus_of[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    cus_of[dev] = n > 0 ? n : 256;
-  }
+  const int cus_dev = device_cus();
+  if (cus_dev == 0) return false;
   // the persistent grid leaves the caller's reserved CUs free (the sharded path while an RCCL all-gather is in flight: its
   // kernels need CUs of their own to overlap with the GEMMs; animate3d_amd/parallel.py)
   const int reserved = a3d_gemm_reserved_cus_of(flags);
-  const int cus = cus_of[dev] - reserved > 32 ? cus_of[dev] - reserved : 32;
+  const int cus = cus_dev - reserved > 32 ? cus_dev - reserved : 32;
   if (!p.vec16 || p.K % 64 != 0 || p.M % PBM != 0 || (p.rowbias && p.rb_div % PBM != 0)) return false;
   // 32-bit DMA offsets
   if (p.ldw % 64 != 0 || (CONV == 0 && p.ldx % 64 != 0)) return false;
@@ -385,7 +398,7 @@ bool plan_persist(const GemmParams& p, int flags, bool allow_split, PPPlan& out)
   const int unit = CONV ? 9 : 1;                       // K-tiles an item may be cut at
   // the PLAN is made for the whole chip whatever the caller reserves: the split factor fixes the order of the K sum, and a launch's result must
   // not depend on how many CUs an in-flight all-gather was given (a smaller grid walks the same work items; tests/test_unet_gpu.py)
-  const int cus_plan = cus_of[dev];
+  const int cus_plan = cus_dev;
   constexpr int OVH = 12;
   int64_t best = -1, best1 = -1;
   int bnb = 0, bS = 1, bnb1 = 0;
@@ -417,18 +430,14 @@ bool plan_persist(const GemmParams& p, int flags, bool allow_split, PPPlan& out)
 // rounds x (128 + BN) per K-tile: the widest tile that keeps the number of rounds lowest wins.  The choice may depend on anything (CU
 // reservation included): every width walks K in the same order, results are bit-identical.
 struct RingPlan { int nb, cus, cus_plan; int64_t cost; };
-#ifndef A3D_RING_VS_PP_PCT
-#define A3D_RING_VS_PP_PCT 75           // a persistent-kernel tile costs ~0.75 x (256 + BN) of the ring kernel's units per K-tile and round (measured: at equal
+constexpr int RING_VS_PP_PCT = 75;      // a persistent-kernel tile costs ~0.75 x (256 + BN) of the ring kernel's units per K-tile and round (measured: at equal
                                         // CU fill the two tie at M = 8192, N = 1280 although the ring tile is 128 rows; profiles/r6_microbench_smallm_ring.log)
-#endif
-constexpr int RING_VS_PP_PCT = A3D_RING_VS_PP_PCT;
 inline bool plan_ring(const GemmParams& p, int flags, RingPlan& out) {
-  if (a3d_gemm_kernel_of(flags) == A3D_GEMM_TILE128 || a3d_gemm_kernel_of(flags) == A3D_GEMM_DIRECT || p.out_f32 || !p.vec16 || p.X2 != nullptr) return false;
+  if (a3d_gemm_kernel_of(flags) == A3D_GEMM_TILE128 || p.out_f32 || !p.vec16 || p.X2 != nullptr) return false;
   if (p.M % 128 != 0 || p.K % 64 != 0 || p.K < 256 || p.ldx % 64 != 0 || p.ldw % 64 != 0) return false;
   if ((uint64_t)p.ldx * 64u >= (1ull << 32) || (uint64_t)p.ldw * 256u >= (1ull << 32)) return false;      // 32-bit piece offsets: 3 x 16 ldx, 9 x 16 ldw bytes
   if (p.rowbias && p.rb_div % 128 != 0) return false;
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, a3d_current_device()) != hipSuccess || n <= 0) n = 256;
+  const int n = device_cus() ? device_cus() : 256;
   const int reserved = a3d_gemm_reserved_cus_of(flags);
   out.cus_plan = n;
   out.cus = n - reserved > 32 ? n - reserved : 32;
@@ -446,10 +455,9 @@ inline bool plan_ring(const GemmParams& p, int flags, RingPlan& out) {
 template <int CONV, int EPI>
 int try_launch_persist(hipStream_t stream, GemmParams& p, int flags) {
   PPPlan pl;
-  if (!plan_persist<CONV, EPI>(p, flags, p.ws != nullptr, pl)) return -1000;
+  if (!plan_persist<CONV, EPI>(p, flags, p.ws != nullptr, pl)) return NOT_ELIGIBLE;
   p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
   p.ksplit = pl.S; p.nk_item = (int)(p.K / 64) / pl.S;
-  p.direct = (CONV == 0 && EPI == EPI_LINEAR && pl.S == 1 && p.X2 == nullptr && a3d_gemm_kernel_of(flags) == A3D_GEMM_DIRECT) ? 1 : 0;
   return A3D_FN(a3d_launch_gemm_pp)(CONV, EPI, pl.nb, stream, p, pl.cus);
 }
 
@@ -475,8 +483,7 @@ int launch_bk(hipStream_t stream, GemmParams& p, int64_t nblk) {
 
 template <int CONV, int EPI = EPI_LINEAR>
 int launch(hipStream_t stream, GemmParams& p, int flags) {
-  if (flags & ~(A3D_GEMM_RESERVED_CUS_MASK | A3D_GEMM_KERNEL_MASK)) return A3D_EINVAL;
-  if (a3d_gemm_kernel_of(flags) > A3D_GEMM_DIRECT) return A3D_EINVAL;
+  if (!gemm_flags_ok(flags)) return A3D_EINVAL;
   if constexpr (CONV == 0 && EPI == EPI_LINEAR) {
     // small token matrices: the LDS-DMA ring kernel (gemm_ring.hip) when the persistent grid would be under-filled or lose to it
     RingPlan rp;
@@ -496,7 +503,7 @@ int launch(hipStream_t stream, GemmParams& p, int flags) {
   }
   {
     const int rc = try_launch_persist<CONV, EPI>(stream, p, flags);
-    if (rc != -1000) return rc;
+    if (rc != NOT_ELIGIBLE) return rc;
   }
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
@@ -509,44 +516,59 @@ int launch(hipStream_t stream, GemmParams& p, int flags) {
   return launch_bk<CONV, EPI, 64>(stream, p, nblk);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-}  // namespace
-
-namespace {
 // workspace query of the *_ws entry points: the bytes a split-K launch of this call would use (0: the call does not split)
 template <int CONV>
 int64_t splitk_ws_bytes(const GemmParams& p, int flags) {
   PPPlan pl;
   GemmParams q = p;
   q.ws = nullptr; q.ws_bytes = 0;
-  if (flags & ~(A3D_GEMM_RESERVED_CUS_MASK | A3D_GEMM_KERNEL_MASK)) return 0;
+  if (!gemm_flags_ok(flags)) return 0;
   if (!plan_persist<CONV, EPI_LINEAR>(q, flags, true, pl) || pl.S <= 1) return 0;
   return pl.tiles_m * pl.tiles_n * pl.S * pl.nb * 65536;
 }
-}  // namespace
 
-static int gemm_entry(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
-                      const float* bias, const void* rowbias, int64_t rb_div, const void* R, int64_t ldr,
-                      void* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, float alpha, float beta, int flags,
-                      void* ws, int64_t ws_bytes, int64_t* ws_needed) {
-  if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return A3D_EINVAL;
-  if (K % 64 != 0 || N % 4 != 0) return A3D_EINVAL;
-  if (ldx % 8 != 0 || ldw % 8 != 0 || ldy % 4 != 0 || (R && ldr % 4 != 0)) return A3D_EINVAL;
-  if (!aligned16(X) || !aligned16(W) || (reinterpret_cast<uintptr_t>(Y) & 7u) || (R && (reinterpret_cast<uintptr_t>(R) & 7u)))
-    return A3D_EINVAL;
-  if (bias && (reinterpret_cast<uintptr_t>(bias) & 15u)) return A3D_EINVAL;
-  if (rowbias && (rb_div <= 0 || (reinterpret_cast<uintptr_t>(rowbias) & 7u))) return A3D_EINVAL;
+// a caller's split-K workspace, if it is usable
+void attach_workspace(GemmParams& p, void* ws, int64_t ws_bytes) {
+  if (ws && ws_bytes > 0 && a3d_aligned(16, ws)) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
+}
+
+// GemmParams of a dense call (a3d_gemm, _ws, a3d_gemm2, _f32out, _geglu); rb_div is kept as given for dense_args_ok.  vec16: the rows of
+// Y / R / rowbias allow 16-byte accesses
+GemmParams dense_params(const void* X, int64_t ldx, const void* W, int64_t ldw, const float* bias, const void* rowbias, int64_t rb_div,
+                        const void* R, int64_t ldr, void* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, float alpha, float beta,
+                        bool out_f32 = false) {
   GemmParams p{};
   p.X = (const uint16_t*)X; p.ldx = ldx; p.W = (const uint16_t*)W; p.ldw = ldw;
   p.bias = bias; p.rowbias = (const uint16_t*)rowbias; p.rb_div = rowbias ? rb_div : 1;
   p.R = (const uint16_t*)R; p.ldr = ldr; p.Y = (uint16_t*)Y; p.ldy = ldy;
-  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
-  p.vec16 = (ldy % 8 == 0) && aligned16(Y) && (!R || (ldr % 8 == 0 && aligned16(R))) && (!rowbias || (N % 8 == 0 && aligned16(rowbias)));
+  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta; p.out_f32 = out_f32;
+  p.vec16 = (ldy * (out_f32 ? 4 : 2) % 16 == 0) && a3d_aligned(16, Y) && (!R || (ldr % 8 == 0 && a3d_aligned(16, R))) &&
+            (!rowbias || (N % 8 == 0 && a3d_aligned(16, rowbias)));
+  return p;
+}
+
+// Preconditions of the dense entry points; what differs between them: y_align = bytes of the widest access through Y, and what N and ldy
+// must be multiples of.  X, W and the fp32 bias are fetched 16 bytes at a time (the bias by LDS-DMA), R and rowbias 8 at least.
+bool dense_args_ok(const GemmParams& p, uintptr_t y_align, int n_div, int ldy_div) {
+  if (!p.X || !p.W || !p.Y || p.M <= 0 || p.N <= 0 || p.K <= 0) return false;
+  if (p.K % 64 != 0 || p.N % n_div != 0) return false;
+  if (p.ldx % 8 != 0 || p.ldw % 8 != 0 || p.ldy % ldy_div != 0 || (p.R && p.ldr % 4 != 0)) return false;
+  if (!a3d_aligned(16, p.X, p.W) || !a3d_aligned(16, p.bias) || !a3d_aligned(y_align, p.Y) || !a3d_aligned(8, p.R, p.rowbias)) return false;
+  return !p.rowbias || p.rb_div > 0;
+}
+
+int gemm_entry(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
+               const float* bias, const void* rowbias, int64_t rb_div, const void* R, int64_t ldr,
+               void* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, float alpha, float beta, int flags,
+               void* ws, int64_t ws_bytes, int64_t* ws_needed) {
+  GemmParams p = dense_params(X, ldx, W, ldw, bias, rowbias, rb_div, R, ldr, Y, ldy, M, N, K, alpha, beta);
+  if (!dense_args_ok(p, 8, 4, 4)) return A3D_EINVAL;
   if (ws_needed) { *ws_needed = splitk_ws_bytes<0>(p, flags); return 0; }
-  if (ws && ws_bytes > 0 && aligned16(ws)) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
+  attach_workspace(p, ws, ws_bytes);
   return launch<0>((hipStream_t)stream, p, flags);
 }
+
+}  // namespace
 
 extern "C" int A3D_FN(a3d_gemm)(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                              const float* bias, const void* rowbias, int64_t rb_div, const void* R, int64_t ldr,
@@ -565,31 +587,19 @@ extern "C" int A3D_FN(a3d_gemm_ws)(a3d_stream_t stream, const void* X, int64_t l
 // concatenates and calls a3d_gemm when this returns A3D_EUNSUPPORTED (small or ragged M, unaligned rows)
 extern "C" int A3D_FN(a3d_gemm2)(a3d_stream_t stream, const void* X, int64_t ldx, const void* X2, int64_t ldx2, int64_t K1,
                               const void* W, int64_t ldw, const float* bias, void* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, int flags) {
-  if (!X || !X2 || !W || !Y || M <= 0 || N <= 0 || K <= 0 || K1 <= 0 || K1 >= K) return A3D_EINVAL;
-  if (K % 64 != 0 || K1 % 64 != 0 || N % 8 != 0) return A3D_EINVAL;
-  if (ldx % 8 != 0 || ldx2 % 8 != 0 || ldw % 8 != 0 || ldy % 8 != 0) return A3D_EINVAL;
-  if (!aligned16(X) || !aligned16(X2) || !aligned16(W) || !aligned16(Y)) return A3D_EINVAL;
-  if (bias && (reinterpret_cast<uintptr_t>(bias) & 15u)) return A3D_EINVAL;
-  if (flags & ~(A3D_GEMM_RESERVED_CUS_MASK | A3D_GEMM_KERNEL_MASK)) return A3D_EINVAL;
+  GemmParams p = dense_params(X, ldx, W, ldw, bias, nullptr, 1, nullptr, 0, Y, ldy, M, N, K, 1.f, 0.f);
+  p.X2 = (const uint16_t*)X2; p.ldx2 = ldx2; p.K1 = K1;
+  if (!dense_args_ok(p, 16, 8, 8) || !X2 || K1 <= 0 || K1 >= K || K1 % 64 != 0 || ldx2 % 8 != 0 || !a3d_aligned(16, X2)) return A3D_EINVAL;
+  if (!gemm_flags_ok(flags)) return A3D_EINVAL;
   if (ldx2 % 64 != 0 || (uint64_t)ldx2 * 16u >= (1ull << 31)) return A3D_EUNSUPPORTED;      // (32-bit DMA offsets, as for X)
-  GemmParams p{};
-  p.X = (const uint16_t*)X; p.ldx = ldx; p.X2 = (const uint16_t*)X2; p.ldx2 = ldx2; p.K1 = K1;
-  p.W = (const uint16_t*)W; p.ldw = ldw; p.bias = bias; p.rb_div = 1; p.Y = (uint16_t*)Y; p.ldy = ldy;
-  p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.beta = 0.f; p.vec16 = 1;
   const int rc = try_launch_persist<0, EPI_LINEAR>((hipStream_t)stream, p, flags);
-  return rc == -1000 ? A3D_EUNSUPPORTED : rc;
+  return rc == NOT_ELIGIBLE ? A3D_EUNSUPPORTED : rc;
 }
 
 extern "C" int A3D_FN(a3d_gemm_f32out)(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                                     const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, float alpha) {
-  if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return A3D_EINVAL;
-  if (K % 64 != 0 || N % 8 != 0 || ldx % 8 != 0 || ldw % 8 != 0 || ldy % 4 != 0) return A3D_EINVAL;
-  if (!aligned16(X) || !aligned16(W) || !aligned16(Y)) return A3D_EINVAL;
-  if (bias && (reinterpret_cast<uintptr_t>(bias) & 15u)) return A3D_EINVAL;
-  GemmParams p{};
-  p.X = (const uint16_t*)X; p.ldx = ldx; p.W = (const uint16_t*)W; p.ldw = ldw;
-  p.bias = bias; p.rb_div = 1; p.Y = (uint16_t*)Y; p.ldy = ldy;
-  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = 0.f; p.vec16 = 1; p.out_f32 = 1;
+  GemmParams p = dense_params(X, ldx, W, ldw, bias, nullptr, 1, nullptr, 0, Y, ldy, M, N, K, alpha, 0.f, /*out_f32=*/true);
+  if (!dense_args_ok(p, 16, 8, 4)) return A3D_EINVAL;
   return launch<0>((hipStream_t)stream, p, 0);
 }
 
@@ -600,8 +610,7 @@ static int conv_entry(a3d_stream_t stream, const void* X, const void* Wp, const 
   if (!X || !Wp || !Y || B <= 0 || H <= 0 || W <= 0) return A3D_EINVAL;
   if (Cin % 64 != 0 || Cout % 4 != 0 || (stride != 1 && stride != 2)) return A3D_EINVAL;
   if (up2x < 0 || up2x > 7 || (up2x > 1 && !(up2x & 1)) || (up2x && stride != 1)) return A3D_EINVAL;
-  if (!aligned16(X) || !aligned16(Wp) || (reinterpret_cast<uintptr_t>(Y) & 7u)) return A3D_EINVAL;
-  if (bias && (reinterpret_cast<uintptr_t>(bias) & 15u)) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Wp) || !a3d_aligned(16, bias) || !a3d_aligned(8, Y)) return A3D_EINVAL;
   if (rowbias && rb_div <= 0) return A3D_EINVAL;
   // up2x bit 0: nearest-2x upsample in front of the conv; bits 1 / 2: the upsampled image is cropped by its last row /
   // column (nearest interpolation to the forced size 2H-1 / 2W-1 of unet_motion_mv_model.py:831-837 is exactly that)
@@ -615,9 +624,9 @@ static int conv_entry(a3d_stream_t stream, const void* X, const void* Wp, const 
   p.Ho = (He + 2 - 3) / stride + 1; p.Wo = (We + 2 - 3) / stride + 1;
   p.M = (int64_t)B * p.Ho * p.Wo; p.N = Cout; p.K = (int64_t)9 * Cin;
   p.alpha = 1.f; p.beta = 1.f;
-  p.vec16 = (Cout % 8 == 0) && aligned16(Y) && (!R || aligned16(R)) && (!rowbias || aligned16(rowbias));
+  p.vec16 = (Cout % 8 == 0) && a3d_aligned(16, Y, R, rowbias);
   if (ws_needed) { *ws_needed = up2x ? splitk_ws_bytes<2>(p, flags) : splitk_ws_bytes<1>(p, flags); return 0; }
-  if (ws && ws_bytes > 0 && aligned16(ws)) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
+  attach_workspace(p, ws, ws_bytes);
   return up2x ? launch<2>((hipStream_t)stream, p, flags) : launch<1>((hipStream_t)stream, p, flags);
 }
 
@@ -636,12 +645,7 @@ extern "C" int A3D_FN(a3d_conv3x3_ws)(a3d_stream_t stream, const void* X, const 
 
 extern "C" int A3D_FN(a3d_gemm_geglu)(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                                    const float* bias, void* Y, int64_t ldy, int64_t M, int64_t N2, int64_t K, int flags) {
-  if (!X || !W || !Y || M <= 0 || N2 <= 0 || K <= 0) return A3D_EINVAL;
-  if (K % 64 != 0 || N2 % 64 != 0 || ldx % 8 != 0 || ldw % 8 != 0 || ldy % 8 != 0) return A3D_EINVAL;
-  if (!aligned16(X) || !aligned16(W) || !aligned16(Y)) return A3D_EINVAL;
-  GemmParams p{};
-  p.X = (const uint16_t*)X; p.ldx = ldx; p.W = (const uint16_t*)W; p.ldw = ldw;
-  p.bias = bias; p.rb_div = 1; p.Y = (uint16_t*)Y; p.ldy = ldy;
-  p.M = M; p.N = N2; p.K = K; p.alpha = 1.f; p.beta = 0.f; p.vec16 = 1;
+  GemmParams p = dense_params(X, ldx, W, ldw, bias, nullptr, 1, nullptr, 0, Y, ldy, M, N2, K, 1.f, 0.f);
+  if (!dense_args_ok(p, 16, 64, 8)) return A3D_EINVAL;
   return launch<0, EPI_GEGLU>((hipStream_t)stream, p, flags);
 }

@@ -43,17 +43,13 @@ template <int NB> struct PPCfg {
   static constexpr int EPI_BYTES = 8 * 32 * 68 * 4;
   static constexpr int STAGE = (XBYTES + WBYTES) > EPI_BYTES ? (XBYTES + WBYTES) : EPI_BYTES;
   static constexpr int BIAS_OFF = 2 * STAGE;
-  static constexpr int BIAS_STRIDE = 2048;
-  static constexpr int SMEM = 2 * STAGE + 2 * BIAS_STRIDE;
+  static constexpr int SMEM = BIAS_OFF + 2 * BIAS_IMG_STRIDE;
 };
 
 // Tile order: groups of PP_GM rows of tiles, column-major inside a group, so that the 32 consecutive tile ids an XCD works on at
 // any time are an 8 x 4 block (8 A panels + 4 W panels per K-tile through that XCD's L2) instead of one row of up to 32 different
 // W panels — the wide projections (N >= 2560: 8-40 column tiles) otherwise stream all of W through every L2 once per row of tiles.
-#ifndef A3D_PP_GM
-#define A3D_PP_GM 8
-#endif
-constexpr int PP_GM = A3D_PP_GM;
+constexpr int PP_GM = 8;
 A3D_DEV void pp_tile_coords(int64_t t, int64_t tiles_m, int64_t tiles_n, int64_t& tile_m, int64_t& tile_n) {
   const int64_t gsz = PP_GM * tiles_n;
   const int64_t blk = t / gsz;
@@ -64,23 +60,15 @@ A3D_DEV void pp_tile_coords(int64_t t, int64_t tiles_m, int64_t tiles_n, int64_t
   tile_m = first + (within - tile_n * gm);
 }
 
-A3D_DEV void pp_barrier() {
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 // Four phases (k-steps of 16) per K-tile; the 4 + NB DMA pieces a wave issues per K-tile go three per phase into phases 0-2 (measured
 // against five-then-the-rest and against two k-steps per phase: profiles/r4_microbench_pp.log).
 // CONV: 0 = dense A, 1 = 3x3 conv gather (pad 1, stride 1|2), 2 = 3x3 conv over a nearest-2x upsampled input
 // SPLIT: split-K work items (GemmParams::ksplit > 1) — a separate instantiation: the item bookkeeping and the fp32 partial stores cost the
 // unsplit kernels registers they do not have (the conv instantiations sit at 256)
 // TWO: two-source A operand (GemmParams::X2; dense only) — its own instantiation for the same reason
-// DIRECT: W rows staged in the permuted order of direct_epilogue (gemm_common.h) and that epilogue instead of the LDS transposition (dense linear
-// epilogues only; A3D_GEMM_DIRECT in the call's flags word)
-template <int CONV, int EPI, int NB, bool RES, bool SPLIT = false, bool TWO = false, bool DIRECT = false>
+template <int CONV, int EPI, int NB, bool RES, bool SPLIT = false, bool TWO = false>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
   static_assert(!TWO || CONV == 0, "the two-source A operand is a dense-GEMM feature");
-  static_assert(!DIRECT || (CONV == 0 && EPI == EPI_LINEAR && !SPLIT && !TWO), "the direct epilogue is a dense linear-epilogue feature");
   using PC = PPCfg<NB>;
   constexpr int PH = 1, NPH = 4;              // k-steps per phase, phases per K-tile
   constexpr int NP = 4 + NB;                  // DMA pieces per wave and K-tile: X 0..3, W 0..NB-1
@@ -104,24 +92,12 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
 
   const uint32_t koff0 = (uint32_t)((g ^ ((l31 >> 1) & 7)) << 4);
   const uint32_t xrd = (uint32_t)(wm * 64 + l31) * 128u;
-  const int wblk = (NB == 5) ? wn * 4 : wn * NB;
-  const int wblk_last = (NB == 5) ? 8 + wn : wn * NB + NB - 1;
-  const uint32_t wrd = (uint32_t)PC::XBYTES + (uint32_t)(wblk * 32 + l31) * 128u;
-  const uint32_t wrd_last = (uint32_t)PC::XBYTES + (uint32_t)(wblk_last * 32 + l31) * 128u;
+  const WaveCols<NB> wc(wn);
+  const uint32_t wrd = (uint32_t)PC::XBYTES + (uint32_t)(wc.first * 32 + l31) * 128u;
+  const uint32_t wrd_last = (uint32_t)PC::XBYTES + (uint32_t)(wc.last * 32 + l31) * 128u;
 
   const uint32_t vx0 = (uint32_t)(lr * p.ldx * 2 + ((pos ^ (lr >> 1)) << 4));
-  // DIRECT: LDS row 8 pc + lr of the W image (MFMA row 8 b + 4 g + c of its 32-block: b = pc & 3, lr = 4 g + c) holds W row
-  // 32 (pc >> 2) + 16 g + 4 b + c: the lane part of the source offset is (16 (lr >> 2) + (lr & 3)) rows, the piece part wro[i]
-  const uint32_t vw0 = DIRECT ? (uint32_t)((16 * (lr >> 2) + (lr & 3)) * p.ldw * 2 + ((pos ^ (lr >> 1)) << 4))
-                              : (uint32_t)(lr * p.ldw * 2 + ((pos ^ (lr >> 1)) << 4));
-  uint32_t wro[DIRECT ? NB : 1];
-  if constexpr (DIRECT) {
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int pc = wid * NB + i;
-      wro[i] = (uint32_t)((32 * (pc >> 2) + 4 * (pc & 3)) * p.ldw * 2);
-    }
-  }
+  const uint32_t vw0 = (uint32_t)(lr * p.ldw * 2 + ((pos ^ (lr >> 1)) << 4));
   uint32_t aoff[CONV ? 4 : 1];
   uint32_t amask[CONV ? 2 : 1];
   // scalar copies of the tap masks: bit set <=> ALL 8 pixels of the piece are inside the image for that tap.  Such a (piece, tap) — 90 % of them
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
     if constexpr (CONV != 0) xck = (uint64_t)(uintptr_t)p.X - (uint64_t)cbias * 2u + (uint64_t)kofs * 2u;
     if constexpr (CONV == 0) xk = (uint64_t)(uintptr_t)(p.X + (ld_m0 + wid * 32) * p.ldx + kofs);
     if constexpr (TWO) xk2 = (uint64_t)(uintptr_t)(p.X2 + (ld_m0 + wid * 32) * p.ldx2);
-    wk = (uint64_t)(uintptr_t)(p.W + (ld_n0 + (DIRECT ? 0 : wid * (NB * 8))) * p.ldw + kofs);
+    wk = (uint64_t)(uintptr_t)(p.W + (ld_n0 + wid * (NB * 8)) * p.ldw + kofs);
     if (EPI == EPI_LINEAR && p.rowbias) rbk = (uint64_t)(uintptr_t)(p.rowbias + (ld_m0 / p.rb_div) * p.N + ld_n0);
     if constexpr (CONV != 0) {
       amask[0] = 0; amask[1] = 0;
@@ -215,13 +191,13 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
     const uint32_t dst = lds0 + (uint32_t)buf * PC::STAGE;
     if constexpr (A == 0) {
       if (ik0 == 0) {
-        const uint32_t bdst = lds0 + (uint32_t)PC::BIAS_OFF + (uint32_t)ld_par * PC::BIAS_STRIDE;
+        const uint32_t bdst = lds0 + (uint32_t)PC::BIAS_OFF + (uint32_t)ld_par * BIAS_IMG_STRIDE;
         if (p.bias) {
           if (wid == 0) glds16_s((uint32_t)lane * 16u, p.bias + ld_n0, bdst);
-          if (NB == 5 && wid == 1) { if (lane < 16) glds16_s((uint32_t)lane * 16u, p.bias + ld_n0 + 256, bdst + 1024u); }
+          if (NB == 5 && wid == 1) { if (lane < 16) glds16_s((uint32_t)lane * 16u, p.bias + ld_n0 + BIAS_IMG_DMA / 4, bdst + (uint32_t)BIAS_IMG_DMA); }
         }
         if (EPI == EPI_LINEAR && p.rowbias && wid == 2) {
-          if (lane < PC::BN / 8) glds16_s((uint32_t)lane * 16u, (const void*)(uintptr_t)rbk, bdst + 1280u);
+          if (lane < PC::BN / 8) glds16_s((uint32_t)lane * 16u, (const void*)(uintptr_t)rbk, bdst + (uint32_t)BIAS_IMG_ROWBIAS);
         }
       }
     }
@@ -262,8 +238,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
     for (int i = 0; i < NB; ++i) {
       if (4 + i < A || 4 + i >= B) continue;
       const int pc = wid * NB + i;
-      const uint32_t wpo = DIRECT ? wro[DIRECT ? i : 0] : (uint32_t)(i * sw8);
-      glds16_s(vw0 ^ (uint32_t)((pc & 1) << 6), (const void*)(uintptr_t)(wk + (uint64_t)wpo), dst + (uint32_t)PC::XBYTES + (uint32_t)pc * 1024u);
+      glds16_s(vw0 ^ (uint32_t)((pc & 1) << 6), (const void*)(uintptr_t)(wk + (uint64_t)(uint32_t)(i * sw8)), dst + (uint32_t)PC::XBYTES + (uint32_t)pc * 1024u);
     }
     if constexpr (B == NP) {
       if constexpr (CONV != 0) {
@@ -310,18 +285,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
   f32x16_t acc[NB][2];
   u32x4_t fx[PH][2], fw[PH][NB];
   auto load_frags = [&](int buf, int ks0) __attribute__((always_inline)) {
-    const char* xs = smem_b + buf * PC::STAGE + xrd;
-    const char* ws = smem_b + buf * PC::STAGE + wrd;
-    const char* wl = smem_b + buf * PC::STAGE + wrd_last;
 #pragma unroll
-    for (int s = 0; s < PH; ++s) {
-      const uint32_t ko = koff0 ^ (uint32_t)((ks0 + s) << 5);
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm) fx[s][tm] = *reinterpret_cast<const u32x4_t*>(xs + tm * 4096 + ko);
-#pragma unroll
-      for (int tn = 0; tn < NB - 1; ++tn) fw[s][tn] = *reinterpret_cast<const u32x4_t*>(ws + tn * 4096 + ko);
-      fw[s][NB - 1] = *reinterpret_cast<const u32x4_t*>(wl + ko);
-    }
+    for (int s = 0; s < PH; ++s) read_frags<NB>(smem_b + buf * PC::STAGE, xrd, wrd, wrd_last, koff0 ^ (uint32_t)((ks0 + s) << 5), fx[s], fw[s]);
   };
   auto mfma_phase = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -332,22 +297,12 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
         for (int tm = 0; tm < 2; ++tm) acc[tn][tm] = mfma32(fw[s][tn], fx[s][tm], acc[tn][tm]);
   };
 
-  // the epilogue reads the per-tile bias (fp32) and rowbias (16-bit) images from LDS unconditionally: a launch without one of them
-  // zero-fills both parities of the image once (+0.0 is what the 128 x 128 kernel adds for an absent bias, too)
-  if (!p.bias || !(EPI == EPI_LINEAR && p.rowbias)) {
-    uint32_t* const bz = reinterpret_cast<uint32_t*>(smem_b + PC::BIAS_OFF);
-    for (int i = tid; i < 2 * PC::BIAS_STRIDE / 4; i += 512) {
-      const int o = (i * 4) % PC::BIAS_STRIDE;                 // byte offset inside one parity: [0, 1280) bias, [1280, 1920) rowbias
-      if ((o < 1280 && !p.bias) || (o >= 1280 && !(EPI == EPI_LINEAR && p.rowbias))) bz[i] = 0u;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    pp_barrier();
-  }
+  zero_absent_bias_images<512>(smem_b + PC::BIAS_OFF, p.bias, EPI == EPI_LINEAR ? p.rowbias : nullptr, tid);      // (GEGLU takes no rowbias)
   // prologue: the first K-tile of the first tile, complete for everybody
   setup_tile(t);
   issue_pieces(0, std::integral_constant<int, 0>{}, std::integral_constant<int, NP>{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  pp_barrier();
+  tile_barrier();
   int buf = 0;
   for (;;) {
     int64_t tile_n, tile_m;
@@ -361,7 +316,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     const int cur_par = ld_par;
-    if (grp) pp_barrier();                         // group 1 runs one barrier behind group 0
+    if (grp) tile_barrier();                         // group 1 runs one barrier behind group 0
     for (int kt = 0; kt < nk; ++kt) {
       const bool last = kt + 1 >= nk;
       const bool more = !last || tnext < ntiles;   // a K-tile follows this one (this tile's next or the next tile's first)
@@ -379,18 +334,18 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
           if constexpr (ph == NPH - 1) { if (grp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        pp_barrier();                              // B1
+        tile_barrier();                              // B1
         // ---- M section
         __builtin_amdgcn_s_setprio(1);
         mfma_phase();
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (ph == NPH - 1) { if (more && !grp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        pp_barrier();                              // B2
+        tile_barrier();                              // B2
       });
       buf ^= 1;
     }
-    if (!grp) pp_barrier();                        // group 0 waits for group 1's last phase: both run the epilogue together
+    if (!grp) tile_barrier();                        // group 0 waits for group 1's last phase: both run the epilogue together
 
     if constexpr (SPLIT) {
       // split-K item: the fp32 accumulators leave in register order (1 KB per store instruction, no LDS); splitk_reduce_kernel reads them back
@@ -403,15 +358,12 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
           for (int q = 0; q < 4; ++q)
             *reinterpret_cast<float4*>(wsi + ((tn * 2 + tm) * 4 + q) * 256) =
                 float4{acc[tn][tm][4 * q], acc[tn][tm][4 * q + 1], acc[tn][tm][4 * q + 2], acc[tn][tm][4 * q + 3]};
-    } else if constexpr (DIRECT) {
-      direct_epilogue<NB, RES>(p, acc, reinterpret_cast<const float*>(smem_b + PC::BIAS_OFF + cur_par * PC::BIAS_STRIDE),
-                               reinterpret_cast<const uint16_t*>(smem_b + PC::BIAS_OFF + cur_par * PC::BIAS_STRIDE + 1280),
-                               m0, n0, wm, wblk, wblk_last, lane);
     } else {
-      persist_epilogue<EPI, NB, RES>(p, acc, reinterpret_cast<float*>(smem_b + (buf ^ 1) * PC::STAGE) + wid * (32 * 68),
-                                     reinterpret_cast<const float*>(smem_b + PC::BIAS_OFF + cur_par * PC::BIAS_STRIDE),
-                                     reinterpret_cast<const uint16_t*>(smem_b + PC::BIAS_OFF + cur_par * PC::BIAS_STRIDE + 1280),
-                                     m0, n0, wm, wblk, wblk_last, lane);
+      float* const stg = reinterpret_cast<float*>(smem_b + (buf ^ 1) * PC::STAGE) + wid * (32 * 68);
+      const float* const bias_lds = bias_image(smem_b + PC::BIAS_OFF, cur_par);
+      const uint16_t* const rowbias_lds = rowbias_image(smem_b + PC::BIAS_OFF, cur_par);
+      if constexpr (EPI == EPI_GEGLU || !RES) epilogue_rounded<EPI, NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
+      else epilogue_residual<NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
     }
     if (tnext >= ntiles) break;
     t = tnext;
@@ -426,8 +378,7 @@ __global__ __launch_bounds__(512) void splitk_reduce_kernel(const GemmParams p) 
   using PC = PPCfg<NB>;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1, l31 = lane & 31, g = lane >> 5;
-  const int wblk = (NB == 5) ? wn * 4 : wn * NB;
-  const int wblk_last = (NB == 5) ? 8 + wn : wn * NB + NB - 1;
+  const WaveCols<NB> wc(wn);
   const int S = p.ksplit;
   int64_t tile_n, tile_m;
   pp_tile_coords(blockIdx.x, p.tiles_m, p.tiles_n, tile_m, tile_n);
@@ -440,7 +391,7 @@ __global__ __launch_bounds__(512) void splitk_reduce_kernel(const GemmParams p) 
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm) {
       const int64_t m = m0 + wm * 64 + tm * 32 + l31;
-      const int64_t nb0 = n0 + (tn < NB - 1 ? wblk + tn : wblk_last) * 32 + 4 * g;
+      const int64_t nb0 = n0 + wc.block(tn) * 32 + 4 * g;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float* src = w0 + ((tn * 2 + tm) * 4 + q) * 256;
@@ -474,16 +425,16 @@ __global__ __launch_bounds__(512) void splitk_reduce_kernel(const GemmParams p) 
     }
 }
 
-template <int CONV, int EPI, int NB, bool RES, bool SPLIT = false, bool TWO = false, bool DIRECT = false>
+template <int CONV, int EPI, int NB, bool RES, bool SPLIT = false, bool TWO = false>
 int launch_pp(hipStream_t stream, const GemmParams& p, int cus) {
   using PC = PPCfg<NB>;
   static uint64_t attr_done = 0;
   if (int rc = a3d_once_per_device(attr_done, [] {
-        return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<CONV, EPI, NB, RES, SPLIT, TWO, DIRECT>),
+        return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<CONV, EPI, NB, RES, SPLIT, TWO>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, PC::SMEM); })) return rc;
   const int64_t ntiles = p.tiles_m * p.tiles_n * (SPLIT ? p.ksplit : 1);
   const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-  gemm_pp_kernel<CONV, EPI, NB, RES, SPLIT, TWO, DIRECT><<<dim3(grid), dim3(512), PC::SMEM, stream>>>(p);
+  gemm_pp_kernel<CONV, EPI, NB, RES, SPLIT, TWO><<<dim3(grid), dim3(512), PC::SMEM, stream>>>(p);
   if (int rc = a3d_launch_status()) return rc;
   if constexpr (SPLIT) {
     splitk_reduce_kernel<NB><<<dim3((unsigned)(p.tiles_m * p.tiles_n), NB), dim3(512), 0, stream>>>(p);
@@ -510,13 +461,6 @@ int launch_pp_conv(int epi, int nb, hipStream_t stream, const GemmParams& p, int
     if (nb == 5) return launch_pp<CONV, EPI_LINEAR, 5, false, true>(stream, p, cus);
     if (nb == 4) return launch_pp<CONV, EPI_LINEAR, 4, false, true>(stream, p, cus);
     return A3D_EUNSUPPORTED;
-  }
-  if constexpr (CONV == 0) {
-    if (p.direct) {            // direct epilogue (A3D_GEMM_DIRECT)
-      if (nb == 5) return p.R ? launch_pp<0, EPI_LINEAR, 5, true, false, false, true>(stream, p, cus) : launch_pp<0, EPI_LINEAR, 5, false, false, false, true>(stream, p, cus);
-      if (nb == 4) return p.R ? launch_pp<0, EPI_LINEAR, 4, true, false, false, true>(stream, p, cus) : launch_pp<0, EPI_LINEAR, 4, false, false, false, true>(stream, p, cus);
-      return A3D_EUNSUPPORTED;
-    }
   }
   if (nb == 5) return p.R ? launch_pp<CONV, EPI_LINEAR, 5, true>(stream, p, cus) : launch_pp<CONV, EPI_LINEAR, 5, false>(stream, p, cus);
   if (nb == 4) return p.R ? launch_pp<CONV, EPI_LINEAR, 4, true>(stream, p, cus) : launch_pp<CONV, EPI_LINEAR, 4, false>(stream, p, cus);

@@ -37,22 +37,16 @@ template <int NB> struct RingCfg {
   static constexpr int RING = NB == 2 ? 4 : (NB == 4 ? 3 : 2);
   static constexpr int AHEAD = RING - 1;
   static constexpr int BIAS_OFF = RING * STAGE;
-  static constexpr int BIAS_STRIDE = 2048;                     // per parity: fp32 bias [0, 1280), 16-bit rowbias row [1280, 1920)
-  static constexpr int SMEM = BIAS_OFF + 2 * BIAS_STRIDE;
+  static constexpr int SMEM = BIAS_OFF + 2 * BIAS_IMG_STRIDE;
   static constexpr int NPW = 2 * NB;                           // W pieces per wave and K-tile (X: 4)
   static constexpr int NP = 4 + NPW;
   static_assert(SMEM <= 160 * 1024, "LDS");
 };
 
-A3D_DEV void ring_barrier() {
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int NB, bool RES>
 __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
   using RC = RingCfg<NB>;
-  constexpr int RBN = RC::BN, R_STAGE = RC::STAGE, R_RING = RC::RING, R_AHEAD = RC::AHEAD, R_BIAS_OFF = RC::BIAS_OFF, R_BIAS_STRIDE = RC::BIAS_STRIDE;
+  constexpr int RBN = RC::BN, R_STAGE = RC::STAGE, R_RING = RC::RING, R_AHEAD = RC::AHEAD, R_BIAS_OFF = RC::BIAS_OFF;
   constexpr int NPW = RC::NPW, NP = RC::NP;
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   char* const smem_b = reinterpret_cast<char*>(smem);
@@ -74,10 +68,9 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
   // fragment read offsets (see gemm_pp.hip)
   const uint32_t koff0 = (uint32_t)((g ^ ((l31 >> 1) & 7)) << 4);
   const uint32_t xrd = (uint32_t)(wm * 64 + l31) * 128u;
-  const int wblk = (NB == 5) ? wn * 4 : wn * NB;
-  const int wblk_last = (NB == 5) ? 8 + wn : wn * NB + NB - 1;
-  const uint32_t wrd = (uint32_t)R_XBYTES + (uint32_t)(wblk * 32 + l31) * 128u;
-  const uint32_t wrd_last = (uint32_t)R_XBYTES + (uint32_t)(wblk_last * 32 + l31) * 128u;
+  const WaveCols<NB> wc(wn);
+  const uint32_t wrd = (uint32_t)R_XBYTES + (uint32_t)(wc.first * 32 + l31) * 128u;
+  const uint32_t wrd_last = (uint32_t)R_XBYTES + (uint32_t)(wc.last * 32 + l31) * 128u;
   // DMA source offsets of a lane inside a piece (8 rows x 128 B, chunk index swizzled by (row >> 1) & 7; row = 8 i + lr)
   const uint32_t vx0 = (uint32_t)(lr * p.ldx * 2 + ((pos ^ (lr >> 1)) << 4));
   const uint32_t vw0 = (uint32_t)(lr * p.ldw * 2 + ((pos ^ (lr >> 1)) << 4));
@@ -103,13 +96,13 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
     if (ik == 0) {
       int64_t tm_, tn_;
       tile_mn(it, tm_, tn_);
-      const uint32_t bdst = lds0 + (uint32_t)R_BIAS_OFF + (uint32_t)ipar * R_BIAS_STRIDE;
+      const uint32_t bdst = lds0 + (uint32_t)R_BIAS_OFF + (uint32_t)ipar * BIAS_IMG_STRIDE;
       if (p.bias) {
         if (wid == 0) { if (lane < (RBN < 256 ? RBN / 4 : 64)) glds16_s((uint32_t)lane * 16u, p.bias + tn_ * RBN, bdst); }
-        if (NB == 5 && wid == 2) { if (lane < 16) glds16_s((uint32_t)lane * 16u, p.bias + tn_ * RBN + 256, bdst + 1024u); }
+        if (NB == 5 && wid == 2) { if (lane < 16) glds16_s((uint32_t)lane * 16u, p.bias + tn_ * RBN + BIAS_IMG_DMA / 4, bdst + (uint32_t)BIAS_IMG_DMA); }
       }
       if (p.rowbias && wid == 1) {
-        if (lane < RBN / 8) glds16_s((uint32_t)lane * 16u, p.rowbias + ((tm_ * RBM) / p.rb_div) * p.N + tn_ * RBN, bdst + 1280u);
+        if (lane < RBN / 8) glds16_s((uint32_t)lane * 16u, p.rowbias + ((tm_ * RBM) / p.rb_div) * p.N + tn_ * RBN, bdst + (uint32_t)BIAS_IMG_ROWBIAS);
       }
     }
 #pragma unroll
@@ -124,16 +117,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
     if (++ik == nk) { ik = 0; it += G; ipar ^= 1; if (iq < total_kt) setup_request(); }
   };
 
-  // launches without a bias / rowbias: the epilogue reads the images unconditionally (zero-filled once)
-  if (!p.bias || !p.rowbias) {
-    uint32_t* const bz = reinterpret_cast<uint32_t*>(smem_b + R_BIAS_OFF);
-    for (int i = tid; i < 2 * R_BIAS_STRIDE / 4; i += 256) {
-      const int o = (i * 4) % R_BIAS_STRIDE;
-      if ((o < 1280 && !p.bias) || (o >= 1280 && !p.rowbias)) bz[i] = 0u;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    ring_barrier();
-  }
+  zero_absent_bias_images<256>(smem_b + R_BIAS_OFF, p.bias, p.rowbias, tid);
 
   setup_request();
 #pragma unroll 1
@@ -142,15 +126,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
   f32x16_t acc[NB][2];
   u32x4_t fx[2][2], fw[2][NB];
   auto load_frags = [&](uint32_t stage_off, int ks, int fb) __attribute__((always_inline)) {
-    const char* xs = smem_b + stage_off + xrd;
-    const char* ws = smem_b + stage_off + wrd;
-    const char* wl = smem_b + stage_off + wrd_last;
-    const uint32_t ko = koff0 ^ (uint32_t)(ks << 5);
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) fx[fb][tm] = *reinterpret_cast<const u32x4_t*>(xs + tm * 4096 + ko);
-#pragma unroll
-    for (int tn = 0; tn < NB - 1; ++tn) fw[fb][tn] = *reinterpret_cast<const u32x4_t*>(ws + tn * 4096 + ko);
-    fw[fb][NB - 1] = *reinterpret_cast<const u32x4_t*>(wl + ko);
+    read_frags<NB>(smem_b + stage_off, xrd, wrd, wrd_last, koff0 ^ (uint32_t)(ks << 5), fx[fb], fw[fb]);
   };
 
   int64_t cq = 0;                         // global index of the K-tile being consumed
@@ -174,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
       if (R_AHEAD >= 3 && behind >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(2 * NP) : "memory");
       else if (R_AHEAD >= 2 && behind >= 1) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(NP) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      ring_barrier();
+      tile_barrier();
       if (iq < total_kt) request();
       const uint32_t stage = cstage * (uint32_t)R_STAGE;
       last_off = stage;
@@ -193,11 +169,12 @@ __global__ __launch_bounds__(256, 1) void gemm_ring_kernel(const GemmParams p) {
         __builtin_amdgcn_sched_barrier(0);
       });
     }
-    ring_barrier();                        // every wave is done with the last stage: the epilogue stages through it
-    persist_epilogue<EPI_LINEAR, NB, RES>(p, acc, reinterpret_cast<float*>(smem_b + last_off) + wid * (32 * 68),
-                                          reinterpret_cast<const float*>(smem_b + R_BIAS_OFF + cpar * R_BIAS_STRIDE),
-                                          reinterpret_cast<const uint16_t*>(smem_b + R_BIAS_OFF + cpar * R_BIAS_STRIDE + 1280),
-                                          m0, n0, wm, wblk, wblk_last, lane);
+    tile_barrier();                        // every wave is done with the last stage: the epilogue stages through it
+    float* const stg = reinterpret_cast<float*>(smem_b + last_off) + wid * (32 * 68);
+    const float* const bias_lds = bias_image(smem_b + R_BIAS_OFF, cpar);
+    const uint16_t* const rowbias_lds = rowbias_image(smem_b + R_BIAS_OFF, cpar);
+    if constexpr (RES) epilogue_residual<NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
+    else epilogue_rounded<EPI_LINEAR, NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
     cpar ^= 1;
   }
 }

@@ -72,15 +72,13 @@ typedef struct a3d_rowmap {
  *   bits 8-9   kernel choice: 0 = automatic (persistent 256-row-tile kernel for the big token matrices; round 6: the LDS-DMA ring kernel
  *              with 128-row tiles for the small ones — UNet levels 2 / 3 of a multi-GPU rank, the 4D-SDS shape —; 128 x 128 register-staged
  *              tiles for ragged shapes), A3D_GEMM_TILE128 = always the register-staged 128 x 128 kernel, A3D_GEMM_RING = the ring kernel
- *              whenever the shape allows it (a3d_gemm only; falls back to the automatic choice otherwise), A3D_GEMM_DIRECT = the persistent
- *              kernel storing straight from the accumulator layout (a3d_gemm only).  All kernels walk K in the same
- *              order with the same epilogue arithmetic: bit-identical results (A/B measurements and the parity tests).  Other bits must be
- *              zero (A3D_EINVAL). */
+ *              whenever the shape allows it (a3d_gemm only; falls back to the automatic choice otherwise).  All kernels walk K in the same order with
+ *              the same epilogue arithmetic: bit-identical results (A/B measurements and the parity tests).  The fourth value of the
+ *              field (0x300) names no kernel, and other bits must be zero (A3D_EINVAL). */
 #define A3D_GEMM_RESERVED_CUS_MASK 0xff
 #define A3D_GEMM_KERNEL_MASK 0x300
 #define A3D_GEMM_TILE128 0x100
 #define A3D_GEMM_RING 0x200
-#define A3D_GEMM_DIRECT 0x300   /* the persistent kernel with its direct (LDS-free) epilogue where the shape allows it: measurement of round 6 */
 int a3d_gemm_bf16(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                   const float* bias, const void* rowbias, int64_t rb_div, const void* R, int64_t ldr,
                   void* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, float alpha, float beta, int flags);
@@ -116,7 +114,8 @@ int a3d_gemm_f32out_bf16(a3d_stream_t stream, const void* X, int64_t ldx, const 
  *   Y[M, N2/2][m, j] = (X·Wh^T + bh)[m, j] * gelu_erf((X·Wg^T + bg)[m, j])
  * W / bias rows must be INTERLEAVED in blocks of 32: rows [64b, 64b+32) = h rows [32b, 32b+32),
  * rows [64b+32, 64b+64) = gate rows [32b, 32b+32), so h and gate of one output column land in the same
- * wave tile and the 2x wider intermediate never goes to HBM.  N2 % 64 == 0, K % 64 == 0. */
+ * wave tile and the 2x wider intermediate never goes to HBM.  N2 % 64 == 0, K % 64 == 0, 16-byte aligned rows and bias (the persistent
+ * kernel fetches the bias by 16-byte LDS-DMA, as a3d_gemm does). */
 int a3d_gemm_geglu_bf16(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                         const float* bias, void* Y, int64_t ldy, int64_t M, int64_t N2, int64_t K, int flags);
 

@@ -240,3 +240,98 @@ def test_deform_field_size_queries(lib):
                  (DG_T, DG_N, _dg_desc(W={3: 1})), (DG_T, DG_N, _dg_desc(H={8: 32769})), (DG_T, DG_N, _dg_desc(off={1: 8})),
                  (DG_T, DG_N, _dg_desc(off={1: -16}))):
         assert ws(*args) == 0, args[:2]
+
+
+# ---- GEMM / implicit-GEMM convolution family (csrc/gemm_conv.hip): one argument check serves the dense entry points, one the convolutions
+GEMM_VALID = dict(ldx=320, ldx2=320, ldw=320, ldr=320, ldy=320, M=256, N=320, K=320, K1=128, rb_div=256, flags=0,
+                  B=2, H=8, W=8, Cin=64, Cout=320, stride=1, up2x=0)
+# entry point -> operand -> bytes of the widest access made through it
+GEMM_OPERANDS = {
+    "a3d_gemm_bf16": dict(X=16, W=16, bias=16, rowbias=8, R=8, Y=8),
+    "a3d_gemm_ws_bf16": dict(X=16, W=16, bias=16, rowbias=8, R=8, Y=8),
+    "a3d_gemm2_bf16": dict(X=16, X2=16, W=16, bias=16, Y=16),
+    "a3d_gemm_f32out_bf16": dict(X=16, W=16, bias=16, Y=16),
+    "a3d_gemm_geglu_bf16": dict(X=16, W=16, bias=16, Y=16),
+    "a3d_conv3x3_bf16": dict(X=16, W=16, bias=16, Y=8),
+    "a3d_conv3x3_ws_bf16": dict(X=16, W=16, bias=16, Y=8),
+}
+GEMM_HAS_FLAGS = sorted(set(GEMM_OPERANDS) - {"a3d_gemm_f32out_bf16"})
+GEMM_WS = ("a3d_gemm_ws_bf16", "a3d_conv3x3_ws_bf16")
+
+
+def _gemm_call(lib, entry, f16, ptr=None, ws_needed=None, **geometry):
+    """The valid launch of `entry` (dense: 256 x 320 x 320, GEGLU: N2 = 640; conv: 2 x 8 x 8 x 64 -> 320) with the named pointers /
+    geometry words replaced.  Callers replace exactly one, and never none (a workspace query launches nothing)."""
+    assert ptr or geometry or ws_needed is not None, "a fully valid call would launch a kernel on made-up addresses"
+    conv = "conv3x3" in entry
+    p = _ptrs(["X", "X2", "W", "bias", "rowbias", "R", "Y", "ws"])
+    p.update(ptr or {})
+    g = dict(GEMM_VALID, **geometry)
+    if conv:
+        args = [None, p["X"], p["W"], p["bias"], p["rowbias"], g["rb_div"], p["R"], p["Y"], g["B"], g["H"], g["W"], g["Cin"], g["Cout"],
+                g["stride"], g["up2x"], g["flags"]]
+    elif entry == "a3d_gemm2_bf16":
+        args = [None, p["X"], g["ldx"], p["X2"], g["ldx2"], g["K1"], p["W"], g["ldw"], p["bias"], p["Y"], g["ldy"], g["M"], g["N"], g["K"], g["flags"]]
+    elif entry == "a3d_gemm_f32out_bf16":
+        args = [None, p["X"], g["ldx"], p["W"], g["ldw"], p["bias"], p["Y"], g["ldy"], g["M"], g["N"], g["K"], 1.0]
+    elif entry == "a3d_gemm_geglu_bf16":
+        args = [None, p["X"], g["ldx"], p["W"], g["ldw"], p["bias"], p["Y"], g["ldy"], g["M"], 2 * g["N"], g["K"], g["flags"]]
+    else:
+        args = [None, p["X"], g["ldx"], p["W"], g["ldw"], p["bias"], p["rowbias"], g["rb_div"], p["R"], g["ldr"], p["Y"], g["ldy"],
+                g["M"], g["N"], g["K"], 1.0, 1.0, g["flags"]]
+    if entry in GEMM_WS:
+        args += [None, 0, ctypes.byref(ws_needed)] if ws_needed is not None else [p["ws"], 1 << 20, None]
+    return getattr(lib, _twin(entry, f16))(*args)
+
+
+GEMM = pytest.mark.parametrize("entry", sorted(GEMM_OPERANDS))
+
+
+@F16
+@GEMM
+def test_gemm_family_refuses_misaligned_operand(lib, entry, f16):
+    """X, W (X2) and the fp32 bias are fetched 16 bytes at a time (the persistent kernel's bias by LDS-DMA: a3d_gemm_geglu included);
+    Y, R and rowbias of a3d_gemm are accessed 8 bytes at a time at least; the outputs of a3d_gemm2, _f32out and _geglu 16."""
+    base = _ptrs(["X", "X2", "W", "bias", "rowbias", "R", "Y", "ws"])
+    for operand, a in GEMM_OPERANDS[entry].items():
+        rc = _gemm_call(lib, entry, f16, ptr={operand: base[operand] + a // 2})
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +{a // 2} bytes returned {rc}"
+
+
+@F16
+@GEMM
+def test_gemm_family_refuses_bad_geometry(lib, entry, f16):
+    """Every divisibility rule of include/animate3d_hip.h, the stride and up2x codes, a rowbias without a positive rb_div, and a flags
+    word with a bit outside the two masks."""
+    if "conv3x3" in entry:
+        bad = [dict(Cin=96), dict(Cin=32), dict(Cout=322), dict(stride=0), dict(stride=3), dict(up2x=-1), dict(up2x=8), dict(up2x=2),
+               dict(up2x=4), dict(up2x=6), dict(up2x=1, stride=2), dict(rb_div=0), dict(rb_div=-256), dict(B=0), dict(H=0), dict(W=0)]
+    else:
+        bad = [dict(K=352), dict(K=32), dict(ldx=324), dict(ldw=324), dict(M=0), dict(N=0), dict(K=0)]
+        bad += {"a3d_gemm_bf16": [dict(N=322), dict(ldy=322), dict(ldr=322), dict(rb_div=0), dict(rb_div=-256)],
+                "a3d_gemm_ws_bf16": [dict(N=322), dict(ldy=322), dict(ldr=322), dict(rb_div=0), dict(rb_div=-256)],
+                "a3d_gemm2_bf16": [dict(N=324), dict(ldy=324), dict(ldx2=324), dict(K1=100), dict(K1=0), dict(K1=320), dict(K1=384)],
+                "a3d_gemm_f32out_bf16": [dict(N=324), dict(ldy=322)],
+                "a3d_gemm_geglu_bf16": [dict(N=336), dict(N=304), dict(ldy=324)]}[entry]        # N2 = 2 N: 672 and 608 are no multiples of 64
+    if entry in GEMM_HAS_FLAGS:
+        bad += [dict(flags=0x400), dict(flags=0x1000 | 8), dict(flags=1 << 30)]
+    for g in bad:
+        assert _gemm_call(lib, entry, f16, **g) == A3D_EINVAL, f"{entry}: {g}"
+
+
+@F16
+@pytest.mark.parametrize("entry", GEMM_HAS_FLAGS)
+def test_gemm_family_refuses_unassigned_kernel_choice(lib, entry, f16):
+    """Kernel choice 0x300 (both bits of A3D_GEMM_KERNEL_MASK) names no kernel."""
+    for flags in (0x300, 0x300 | 16):
+        assert _gemm_call(lib, entry, f16, flags=flags) == A3D_EINVAL, f"{entry}: flags {flags:#x}"
+
+
+@F16
+@pytest.mark.parametrize("entry", GEMM_WS)
+def test_gemm_family_ws_query_with_invalid_flags(lib, entry, f16):
+    """The workspace query of a call whose flags word would be refused answers 0 bytes ("does not split") and no error."""
+    for flags in (0x400, 0x1000 | 8, 1 << 30, 0x300):
+        need = ctypes.c_int64(-1)
+        assert _gemm_call(lib, entry, f16, ws_needed=need, flags=flags) == 0, f"{entry}: flags {flags:#x}"
+        assert need.value == 0, f"{entry}: flags {flags:#x} -> {need.value} bytes"
