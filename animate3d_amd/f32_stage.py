@@ -1,4 +1,4 @@
-"""The host layer shared by the fp32 4-D stage (``splat``, ``deform4d``, ``arap``): how its entry points are launched, what its inputs must
+"""The host layer shared by the fp32 4-D stage (``splat``, ``deform4d``, ``arap``, ``stage4d``): how its entry points are launched, what its inputs must
 be, how work cached per tensor is keyed, and the gather plan its atomic-free backward passes read.  No kernel of its own."""
 from __future__ import annotations
 

@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanimate3d_hip.so")
 _lib = None
 
-c_i64, c_int, c_f32, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+c_i64, c_int, c_f32, c_f64, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
 
 class _RowMapC(ctypes.Structure):
@@ -135,6 +135,9 @@ _SIGNATURES = {
     "a3d_knn_f32": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_f32, c_vp, c_vp]),
     "a3d_arap_energy_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_arap_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # reconstruction loss of the 4-D stage (csrc/recon_loss.hip): fp32 only, no storage twins
+    "a3d_recon_loss_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
+    "a3d_recon_loss_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins
     "a3d_clip_preprocess_lds_limit": (c_i64, []),
     "a3d_clip_preprocess": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,

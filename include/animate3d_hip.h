@@ -478,6 +478,27 @@ int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, int S, cons
                           const int* nn_idx, const float* weight, const int* sample_idx, const double* rot, const int* order,
                           const int* starts, const float* grad_out, float* d_targets, float* d_source);
 
+/* Reconstruction loss of the 4-D stage (csrc/recon_loss.hip; contract in animate3d_amd/stage4d.py, masked_recon_loss), fp32.  Replaces the
+ * val[sampled_idx] copies, the mask compositing and the two F.mse_loss of custom/threestudio-animate3d/systems/animate3d.py:160-184 and the
+ * clamp of diff_gaussian_rasterizer_advanced_4d.py:180.  image [B, 3, H, W] planar and unclamped, alpha [B, H, W], gt_rgb [S, H, W, 3]
+ * interleaved, gt_mask [S, H, W] bytes (non-zero: inside), index [B] int32 or NULL (identity): image b is compared with frame index[b],
+ * which the kernels do not range-check.  bg: the background of all three channels.
+ *   a3d_recon_loss_f32      out [3] = {lambda_rgb mean_rgb + lambda_mask mean_mask, mean_rgb, mean_mask} with
+ *                           mean_rgb = mean((clamp(image, 0, 1) - (m ? gt : bg))^2) over B H W 3 and mean_mask = mean((alpha - m)^2) over
+ *                           B H W.  partials [2, n_partials] fp32 workspace, n_partials = B * ceil(H W / 2048) (anything else: A3D_EINVAL).
+ *                           No atomics: per-thread runs of 8 pixels, a fixed tree per block, the partials added in index order
+ *   a3d_recon_loss_bwd_f32  recomputes from the inputs: d_image = g coef_rgb (clamp(image) - (m ? gt : bg)) where 0 <= image <= 1 and
+ *                           exactly 0 elsewhere, d_alpha = g coef_mask (alpha - m), g = grad_out[0] read on the device; the caller passes
+ *                           coef_rgb = 2 lambda_rgb / (3 B H W), coef_mask = 2 lambda_mask / (B H W).  One of d_image / d_alpha may be NULL
+ * Pointers are 4-byte aligned at least (A3D_EINVAL otherwise); where H W % 4 == 0 and every float pointer is 16-byte aligned the kernels
+ * read and write 16 bytes at a time.  B, H, W > 0 and B H W < 2^40 (A3D_EINVAL), checked before the first HIP call. */
+int a3d_recon_loss_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* alpha, const float* gt_rgb,
+                       const uint8_t* gt_mask, const int* index, float bg, double lambda_rgb, double lambda_mask, float* partials,
+                       int64_t n_partials, float* out);
+int a3d_recon_loss_bwd_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* alpha, const float* gt_rgb,
+                           const uint8_t* gt_mask, const int* index, float bg, float coef_rgb, float coef_mask, const float* grad_out,
+                           float* d_image, float* d_alpha);
+
 /* CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip; contract in animate3d_amd/clip.py, preprocess_frames).
  * Replaces the device -> host -> PIL -> CLIPImageProcessor -> device round trip of animatemv_guidance.py:546-555 / utils/util.py:268-287,
  * bit-equal to it: (uint8)(v * 255.0f), Pillow's 8-bit bicubic resampler (integer, 22 precision bits, horizontal then vertical pass, a
