@@ -48,6 +48,17 @@ def mask_radius(idx, dist, radius, least_edge_num=3):
     return idx, dist
 
 
+def near_ties(pts, idx, dist, radius=None):
+    """[N] bool: the points of which two consecutive neighbour distances (other than those of bitwise twins) or a distance and
+    ``radius ** 2`` lie within the relative gap TIE_GAP."""
+    gap = dist[:, 1:] - dist[:, :-1]
+    twins = (pts[idx[:, 1:]] == pts[idx[:, :-1]]).all(-1)
+    bad = ((gap <= TIE_GAP * dist[:, 1:]) & ~twins).any(1)
+    if radius is not None:
+        bad |= ((dist - radius ** 2).abs() <= TIE_GAP * radius ** 2).any(1)
+    return bad
+
+
 def make_points(N, K, seed, radius=None, duplicates=6, device="cpu", max_rounds=40, extra_bad=None):
     """[N, 3] float64 points in [-0.5, 0.5]^3 holding fp32 values, with ``duplicates`` bitwise copies (one of them a triple), free of near-ties
     among the first K + 2 neighbour distances and of distances at ``radius ** 2``; ``extra_bad(points) -> [N] bool`` names further points to
@@ -65,11 +76,7 @@ def make_points(N, K, seed, radius=None, duplicates=6, device="cpu", max_rounds=
     for rounds in range(1, max_rounds + 1):
         pts[dst] = pts[src]
         idx, dist = knn_bruteforce(pts, K + 2)
-        gap = dist[:, 1:] - dist[:, :-1]
-        twins = (pts[idx[:, 1:]] == pts[idx[:, :-1]]).all(-1)
-        bad = ((gap <= TIE_GAP * dist[:, 1:]) & ~twins).any(1)
-        if radius is not None:
-            bad |= ((dist - radius ** 2).abs() <= TIE_GAP * radius ** 2).any(1)
+        bad = near_ties(pts, idx, dist, radius)
         if extra_bad is not None:
             bad |= extra_bad(pts)
         bad[src] |= bad[dst]                                                        # a copy is drawn again through its original
@@ -78,6 +85,43 @@ def make_points(N, K, seed, radius=None, duplicates=6, device="cpu", max_rounds=
             return pts, rounds, idx, dist
         pts[bad] = draw(n_bad)
     raise RuntimeError(f"make_points: {n_bad} points still sit at a tie after {max_rounds} rounds")
+
+
+def knn_exact(points, K):
+    """(idx [N, K] int64, dist [N, K] float64): the K nearest other points from the full N x N float64 distance matrix, +inf on its
+    diagonal, each row stable-argsorted.  The columns are in index order, so this is the (distance, index) order for ties of any
+    multiplicity (``knn_bruteforce`` ranks ``slack`` extra candidates only: a lattice's 6- and 12-fold ties are beyond it).  N <= 4096."""
+    N = points.shape[0]
+    assert N <= 4096, "knn_exact holds the N x N matrix"
+    p = points.double()
+    d = (p[:, None, 0] - p[None, :, 0]) ** 2 + (p[:, None, 1] - p[None, :, 1]) ** 2 + (p[:, None, 2] - p[None, :, 2]) ** 2
+    d.fill_diagonal_(math.inf)
+    idx = torch.argsort(d, dim=1, stable=True)[:, :K]
+    return idx, d.gather(1, idx)
+
+
+LATTICE_RADIUS = 0.125          # r^2 = 4 / 256: exactly the squared distance of the lattice's fourth shell
+
+
+def lattice_points(seed=23):
+    """The 11^3 = 1331 points (i - 5) / 16 in a seeded random order, so that tied candidates sit in both 1024-point tiles of the search.
+    Squared distances are m / 256 with shells of 6 (m = 1), 12 (m = 2), 8 (m = 3) and 6 (m = 4) points around an interior point: exact in
+    fp32, fused or not."""
+    i = torch.arange(11, dtype=torch.float64)
+    pts = (torch.stack(torch.meshgrid(i, i, i, indexing="ij"), dim=-1).reshape(-1, 3) - 5.0) / 16.0
+    return pts[torch.randperm(len(pts), generator=torch.Generator().manual_seed(seed))]
+
+
+def tile_boundary_points(seed=17, K=16):
+    """(points [2049, 3], idx [2049, K + 2], dist): a tie-free cloud in which points 1023 and 1024, the last of the search's first tile
+    and the first of its second, are bitwise equal and the two nearest of point 0; point 2048, alone in the third tile, is its third."""
+    pts = make_points(2049, K, seed, duplicates=0)[0]
+    pts[1023] = pts[1024] = (pts[0] + torch.tensor([2.0 ** -10, 0.0, 0.0], dtype=torch.float64)).float().double()
+    pts[2048] = (pts[0] + torch.tensor([0.0, 2.0 ** -9, 0.0], dtype=torch.float64)).float().double()
+    idx, dist = knn_exact(pts, K + 2)
+    if bool(near_ties(pts, idx, dist).any()):
+        raise RuntimeError("tile_boundary_points: the planted points made a near-tie; choose another seed")
+    return pts, idx, dist
 
 
 def edges(p, nn_idx):
@@ -167,6 +211,24 @@ SCENES = {
 }
 
 
+def worst_conditioning(source, targets, nn_idx, weight, sample_idx):
+    """[S]: the smallest ``conditioning`` of each sample over the frames, with ``weight`` and with the default weight."""
+    return torch.minimum(conditioning(source, targets, nn_idx, weight, sample_idx),
+                         conditioning(source, targets, nn_idx, default_weight(nn_idx, source.dtype), sample_idx)).min(0).values
+
+
+def resample_ill_conditioned(source, targets, nn_idx, weight, sample_idx, g, max_rounds=40):
+    """Replaces in ``sample_idx``, in place, every sample whose conditioning is below COND in some frame by another draw from ``g``, until
+    none is left.  Returns the rounds taken."""
+    for rounds in range(1, max_rounds + 1):
+        bad = worst_conditioning(source, targets, nn_idx, weight, sample_idx) < COND
+        n_bad = int(bad.sum())
+        if n_bad == 0:
+            return rounds
+        sample_idx[bad] = torch.randint(source.shape[0], (n_bad,), generator=g).to(sample_idx.device)
+    raise RuntimeError(f"{n_bad} ill-conditioned samples after {max_rounds} rounds")
+
+
 def make_scene(Nv, K, generic, S, seed, radius=None, device="cpu", max_rounds=40):
     """dict(source [Nv, 3], targets [3 + generic, Nv, 3], nn_idx [Nv, K] (some -1), weight [Nv, K], sample_idx [S] (with repeats), rounds), float64
     tensors holding fp32 values.  Frame 0 is bitwise the source, frame 1 has its x axis copied from the source, frame 2 is mirrored
@@ -183,22 +245,182 @@ def make_scene(Nv, K, generic, S, seed, radius=None, device="cpu", max_rounds=40
     weight = (torch.rand(Nv, K, generator=g) + 0.25).float().double().to(device)
     weight = weight * (nn_idx >= 0)
     sample_idx = torch.randint(Nv, (S,), generator=g).to(device)
-    rounds = 0
-    for rounds in range(1, max_rounds + 1):
-        cond = torch.minimum(conditioning(source, targets, nn_idx, weight, sample_idx),
-                             conditioning(source, targets, nn_idx, default_weight(nn_idx, source.dtype), sample_idx))
-        bad = (cond < COND).any(0)
-        n_bad = int(bad.sum())
-        if n_bad == 0:
-            break
-        sample_idx[bad] = torch.randint(Nv, (n_bad,), generator=g).to(device)
-    else:
-        raise RuntimeError(f"make_scene: {n_bad} ill-conditioned samples after {max_rounds} rounds")
+    rounds = resample_ill_conditioned(source, targets, nn_idx, weight, sample_idx, g, max_rounds=max_rounds)
     sample_idx[-8:] = sample_idx[:8]                                                # repeats (of well-conditioned samples)
     return dict(source=source, targets=targets, nn_idx=nn_idx, weight=weight, sample_idx=sample_idx, rounds=rounds)
 
 
+def _as_f32(t):
+    return t.float().double()
+
+
+def make_k1(Nv, S, frames, seed):
+    """K = 1: every covariance has rank 1, so R is any rotation that takes the source edge's direction to the target edge's.  The loss
+    (sum w (|t| - |s|)^2) and both gradients do not depend on the choice.  Frame 0 is bitwise the source."""
+    g = torch.Generator().manual_seed(seed)
+    source, _, idx, _ = make_points(Nv, 1, seed, duplicates=0)
+    nn_idx = idx[:, :1].clone()
+    targets = _as_f32(torch.stack([source.clone()] + [deform(source, seed + 100 + i, mirror=i == 1) for i in range(frames - 1)]))
+    weight = _as_f32(torch.rand(Nv, 1, generator=g) + 0.25)
+    sample_idx = torch.randperm(max(S, Nv), generator=g)[:S] % Nv
+    if S >= 16:
+        sample_idx[-8:] = sample_idx[:8]
+    return dict(source=source, targets=targets, nn_idx=nn_idx, weight=weight, sample_idx=sample_idx, rounds=1)
+
+
+AXES_SHIFT = (0.25, -0.5, 0.125)
+
+
+def make_axes(Nv, S, seed, marked=24):
+    """K = 3 on a source quantised to multiples of 2^-12.  Frames: 0 only y copied from the source, 1 only z, 2 x copied except on the
+    vertices ``marked`` (a sample is unchanged there exactly when its star misses them), 3 the source translated by AXES_SHIFT (every
+    edge equal exactly, in fp32 and in fp64)."""
+    g = torch.Generator().manual_seed(seed)
+    source = torch.round(make_points(Nv, 3, seed, duplicates=0)[0] * 4096.0) / 4096.0
+    nn_idx = knn_exact(source, 3)[0]
+    frames = [deform(source, seed + 100 + i) for i in range(3)]
+    frames[0][:, 1] = source[:, 1]
+    frames[1][:, 2] = source[:, 2]
+    mark = torch.randperm(Nv, generator=g)[:marked]
+    x = frames[2][:, 0].clone()
+    frames[2][:, 0] = source[:, 0]
+    frames[2][mark, 0] = x[mark]
+    frames.append(source + torch.tensor(AXES_SHIFT, dtype=torch.float64))
+    targets = _as_f32(torch.stack(frames))
+    weight = _as_f32(torch.rand(Nv, 3, generator=g) + 0.25)
+    sample_idx = torch.randint(Nv, (S,), generator=g)
+    sample_idx[:marked] = mark
+    rounds = resample_ill_conditioned(source, targets, nn_idx, weight, sample_idx, g)
+    return dict(source=source, targets=targets, nn_idx=nn_idx, weight=weight, sample_idx=sample_idx, rounds=rounds, marked=mark)
+
+
+def make_isolated(Nv, K, S, seed, isolated=12):
+    """``isolated`` vertices have a row of -1 and are nobody's neighbour, and sit at fixed positions of ``sample_idx`` (``planted``);
+    ``weight`` is NOT masked: it is non-zero on the absent edges too (``weight_masked`` is the masked one)."""
+    g = torch.Generator().manual_seed(seed)
+    source = make_points(Nv, K, seed, duplicates=0)[0]
+    iso = torch.arange(isolated) * (Nv // isolated) + 3
+    rest = torch.ones(Nv, dtype=torch.bool)
+    rest[iso] = False
+    rest = torch.nonzero(rest)[:, 0]
+    nn_idx = torch.full((Nv, K), -1, dtype=torch.int64)
+    nn_idx[rest] = rest[knn_exact(source[rest], K)[0]]
+    drop = torch.rand(Nv, generator=g) < 0.15
+    nn_idx[drop, K - 1] = -1
+    targets = _as_f32(torch.stack([source.clone(), deform(source, seed + 100), deform(source, seed + 101, amplitude=0.005, mirror=True),
+                                   deform(source, seed + 102, amplitude=0.02)]))
+    weight = _as_f32(torch.rand(Nv, K, generator=g) + 0.25)
+    sample_idx = torch.randint(Nv, (S,), generator=g)
+    planted = torch.arange(isolated) * (S // isolated) + 1
+    sample_idx[planted] = iso
+    rounds = resample_ill_conditioned(source, targets, nn_idx, weight, sample_idx, g)      # a sample without edges is unchanged: it stays
+    return dict(source=source, targets=targets, nn_idx=nn_idx, weight=weight, weight_masked=weight * (nn_idx >= 0), sample_idx=sample_idx,
+                rounds=rounds, isolated=iso, planted=planted)
+
+
+DIAGONAL_LENGTHS = (1.0 / 32, 3.0 / 64, 1.0 / 16)
+DIAGONAL_MAPS = ((1.125, 0.875, 0.9375), (-1.125, 0.875, 0.9375), (1.125, -0.875, 0.9375), (1.125, 0.875, -0.9375))
+
+
+def make_diagonal():
+    """Six stars of three edges ``l_k e_k`` along the axes, one per permutation of DIAGONAL_LENGTHS; frame f is ``D_f p`` with D_f the
+    diagonal DIAGONAL_MAPS[f].  S = diag(l_k^2 d_k) exactly: the Jacobi sweeps find nothing to rotate and only the ordering of the columns
+    and the flip act.  All six orderings of |l_k^2 d_k| occur (the squared lengths are 1 : 2.25 : 4, the |d_k| within 1 : 1.29), each with
+    no and with one negative d_k.  ``R_closed`` [F, S, 3, 3]: diag(sign d_k), the sign of the smallest |l_k^2 d_k| negated where one d_k is
+    negative."""
+    import itertools
+    perms = list(itertools.permutations(range(3)))
+    Nv = 4 * len(perms)
+    source = torch.zeros(Nv, 3, dtype=torch.float64)
+    nn_idx = torch.full((Nv, 3), -1, dtype=torch.int64)
+    lengths = torch.zeros(len(perms), 3, dtype=torch.float64)
+    for i, perm in enumerate(perms):
+        centre = torch.tensor([(i % 3 - 1) * 0.25, (i // 3) * 0.5 - 0.25, 0.125 * i - 0.375], dtype=torch.float64)
+        source[4 * i:4 * i + 4] = centre
+        for k in range(3):
+            lengths[i, k] = DIAGONAL_LENGTHS[perm[k]]
+            source[4 * i + 1 + k, k] -= lengths[i, k]
+            nn_idx[4 * i, k] = 4 * i + 1 + k
+    D = torch.tensor(DIAGONAL_MAPS, dtype=torch.float64)
+    targets = _as_f32(source[None] * D[:, None, :])
+    sample_idx = (torch.arange(2 * len(perms)) % len(perms)) * 4
+    a = lengths[sample_idx // 4][None] ** 2 * D[:, None, :]                          # [F, S, 3]
+    sign = torch.sign(a)
+    smallest = torch.nn.functional.one_hot(a.abs().argmin(-1), 3).bool()
+    sign = torch.where(smallest & (sign.prod(-1, keepdim=True) < 0), -sign, sign)
+    return dict(source=source, targets=targets, nn_idx=nn_idx, weight=default_weight(nn_idx, torch.float64), sample_idx=sample_idx, rounds=1,
+                R_closed=torch.diag_embed(sign))
+
+
+def make_near_rigid(Nv, K, S, frames, seed, noise=1e-4):
+    """Each frame is one exact rotation of the source plus a translation plus ``noise`` Gaussian noise: ``tgt - R src`` is a small
+    difference of large terms, the case the kernels' fp64 interior is there for.  No duplicates, no absent edges."""
+    g = torch.Generator().manual_seed(seed)
+    source, _, idx, _ = make_points(Nv, K, seed, duplicates=0)
+    nn_idx = idx[:, :K].clone()
+    out = []
+    for _ in range(frames):
+        A = torch.linalg.qr(torch.randn(3, 3, generator=g, dtype=torch.float64))[0]
+        if torch.det(A) < 0:
+            A = A * torch.tensor([1.0, 1.0, -1.0], dtype=torch.float64)
+        out.append(source @ A.T + (torch.rand(3, generator=g, dtype=torch.float64) - 0.5) * 0.2
+                   + noise * torch.randn(Nv, 3, generator=g, dtype=torch.float64))
+    targets = _as_f32(torch.stack(out))
+    weight = _as_f32(torch.rand(Nv, K, generator=g) + 0.25)
+    sample_idx = torch.randint(Nv, (S,), generator=g)
+    rounds = resample_ill_conditioned(source, targets, nn_idx, weight, sample_idx, g)
+    return dict(source=source, targets=targets, nn_idx=nn_idx, weight=weight, sample_idx=sample_idx, rounds=rounds)
+
+
+def make_hub(Nv, K, seed, max_rounds=40):
+    """A star graph: vertex 0 is the first neighbour of every other vertex (the others are the nearest), and ``sample_idx`` is every vertex
+    twice, so vertex 0's inverse list has about 2 Nv entries.  ``sample_idx`` is fixed, so an ill-conditioned vertex is drawn again itself."""
+    g = torch.Generator().manual_seed(seed)
+    pts = _as_f32(torch.rand(Nv, 3, generator=g) - 0.5)
+    pts[0] = 0.0                                                                    # in the middle: the edges to it are the shortest they can be
+    weight = _as_f32(torch.rand(Nv, K, generator=g) + 0.25)
+    sample_idx = torch.arange(Nv).repeat(2)
+    for rounds in range(1, max_rounds + 1):
+        near = knn_exact(pts, K)[0]
+        nn_idx = near.clone()
+        for v in range(1, Nv):
+            nn_idx[v] = torch.cat([torch.zeros(1, dtype=torch.int64), near[v][near[v] != 0][:K - 1]])
+        targets = _as_f32(torch.stack([deform(pts, seed + 100), deform(pts, seed + 101, amplitude=0.02)]))
+        bad = worst_conditioning(pts, targets, nn_idx, weight, sample_idx[:Nv]) < COND
+        if bad[0]:                                                                  # vertex 0 stays in the middle: its neighbours move
+            bad[near[0]], bad[0] = True, False
+        n_bad = int(bad.sum())
+        if n_bad == 0:
+            return dict(source=pts, targets=targets, nn_idx=nn_idx, weight=weight, sample_idx=sample_idx, rounds=rounds)
+        pts[bad] = _as_f32(torch.rand(n_bad, 3, generator=g) - 0.5)
+    raise RuntimeError(f"make_hub: {n_bad} ill-conditioned vertices after {max_rounds} rounds")
+
+
+# the scenes of tests/test_arap_edges_gpu.py; with SCENES, every scene an energy test compares on: (maker, its arguments).  Sizes are the
+# smallest at which each seam exists: 128 (frame, sample) pairs per forward block, 256 per stride of the reduction, 256 vertices per
+# backward block.  tests/test_arap_host.py checks on the CPU that each holds the feature it is named for.
+EDGE_SCENES = {
+    "k2": (make_scene, dict(Nv=600, K=2, generic=1, S=129, seed=41)),
+    "k16_radius": (make_scene, dict(Nv=700, K=16, generic=1, S=257, seed=42, radius=0.12)),
+    "k5_nv255": (make_scene, dict(Nv=255, K=5, generic=1, S=127, seed=45)),
+    "k5_nv256": (make_scene, dict(Nv=256, K=5, generic=1, S=127, seed=44)),
+    "k5_nv257": (make_scene, dict(Nv=257, K=5, generic=1, S=127, seed=43)),
+    "k1": (make_k1, dict(Nv=300, S=200, frames=4, seed=46)),
+    "k1_nv2": (make_k1, dict(Nv=2, S=2, frames=3, seed=47)),
+    "axes": (make_axes, dict(Nv=400, S=200, seed=48)),
+    "isolated": (make_isolated, dict(Nv=400, K=4, S=150, seed=49)),
+    "diagonal": (make_diagonal, dict()),
+    "near_rigid": (make_near_rigid, dict(Nv=600, K=3, S=256, frames=3, seed=50)),
+    "hub": (make_hub, dict(Nv=150, K=4, seed=51)),
+}
+RANK_ONE = ("k1", "k1_nv2")     # R is not unique there: compared by its defining properties, not with the oracle
+
+
 def named_scene(name, device="cpu"):
+    """The scene ``name`` of SCENES or EDGE_SCENES (the latter on the CPU)."""
+    if name in EDGE_SCENES:
+        maker, kwargs = EDGE_SCENES[name]
+        return maker(**kwargs)
     Nv, K, generic, S, seed, radius = SCENES[name]
     return make_scene(Nv, K, generic, S, seed, radius=radius, device=device)
 
@@ -206,8 +428,8 @@ def named_scene(name, device="cpu"):
 def run(scene, dtype, device=None, weighted=True, need_source_grad=True):
     """loss, R, unchanged, d_targets, d_source of the restatement in ``dtype``."""
     dev = device or scene["source"].device
-    src = scene["source"].to(dev, dtype).requires_grad_(need_source_grad)
-    tgt = scene["targets"].to(dev, dtype).requires_grad_(True)
+    src = scene["source"].detach().to(dev, dtype, copy=True).requires_grad_(need_source_grad)        # copies: the scene stays as it was made
+    tgt = scene["targets"].detach().to(dev, dtype, copy=True).requires_grad_(True)
     w = scene["weight"].to(dev, dtype) if weighted else None
     loss, R, un = energy(src, tgt, scene["nn_idx"].to(dev), w, scene["sample_idx"].to(dev))
     grads = torch.autograd.grad(loss, [tgt] + ([src] if need_source_grad else []))

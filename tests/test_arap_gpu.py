@@ -26,20 +26,24 @@ def _rel(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
 
 
-def _check_graph(pts64, idx64, dist64, radius, tag):
+def _check_graph(pts64, idx64, dist64, radius, tag, Ks=(1, 3, 10, 16), least_edge_num=3, exact=False):
+    """``knn_graph`` for every K of ``Ks``, without a radius and with ``radius``: ``nn_idx`` equal to the float64 oracle's, the distances
+    within 8 * 2^-24 of it (``exact``: equal to it)."""
     x = pts64.float().cuda()
-    for K in (1, 3, 10, 16):
-        for r in (None, radius):
-            got_i, got_d = arap.knn_graph(x, K, radius=r)
-            want_i, want_d = arap_ref.mask_radius(idx64[:, :K], dist64[:, :K], r)
+    for K in Ks:
+        for r in dict.fromkeys((None, radius)):
+            got_i, got_d = arap.knn_graph(x, K, radius=r, least_edge_num=least_edge_num)
+            want_i, want_d = arap_ref.mask_radius(idx64[:, :K], dist64[:, :K], r, least_edge_num)
             torch.cuda.synchronize()
             wrong = int((got_i.long().cpu() != want_i.cpu()).any(1).sum())
             fin = torch.isfinite(want_d.cpu())
             assert torch.equal(torch.isfinite(got_d.cpu()), fin)
-            err = float(((got_d.double().cpu() - want_d.cpu())[fin].abs() / want_d.cpu()[fin].clamp_min(1e-300)).max())
-            print(f"[arap knn {tag} K {K} radius {r}] points with a wrong neighbour {wrong} / {len(x)}; cut {int((want_i < 0).sum())}; "
-                  f"distance max rel err {err:.3e}")
+            err = float(((got_d.double().cpu() - want_d.cpu())[fin].abs() / want_d.cpu()[fin].clamp_min(1e-300)).max()) if fin.any() else 0.0
+            print(f"[arap knn {tag} K {K} radius {r} least {least_edge_num}] points with a wrong neighbour {wrong} / {len(x)}; "
+                  f"cut {int((want_i < 0).sum())}; distance max rel err {err:.3e}")
             assert wrong == 0 and got_i.dtype == torch.int32 and err <= 8 * 2.0 ** -24
+            assert got_i.shape == got_d.shape == (len(x), K) and got_d.dtype == torch.float32
+            assert not exact or torch.equal(got_d.double().cpu(), want_d.cpu())
             assert bool((got_i.cpu() != torch.arange(len(x))[:, None]).all())            # never its own neighbour
 
 
@@ -84,23 +88,36 @@ def _run_hip(scene, weighted, need_source_grad=True, strided=False):
     return dict(loss=loss.detach(), R=R, d_targets=d_t, d_source=grads[1] if need_source_grad else None), grads[0]
 
 
+def check_against_float64(tag, got, r64, r32, keys=("loss", "R", "d_targets", "d_source"), floor_only=False):
+    """The acceptance rule of the energy tests.  The float32 and the float64 restatement take every unchanged flag alike, so that e32, the
+    relative L2 of the float32 one against the float64 one, measures rounding only; per tensor of ``keys`` the kernels' relative L2 against
+    float64 is at most max(4 e32, FLOOR), with ``floor_only`` at most FLOOR: an fp64 result rounded once to fp32.  A tensor the run did
+    not ask for (``d_source`` without ``source.requires_grad``) is None on both sides.  Returns the worst error as a fraction of its bar."""
+    assert torch.equal(r64["unchanged"], r32["unchanged"])                              # e32 below measures rounding only
+    failures, worst = [], 0.0
+    for k in keys:
+        if r64[k] is None:
+            assert got[k] is None, k
+            continue
+        e32, err = _rel(r32[k], r64[k]), _rel(got[k], r64[k])
+        bar = FLOOR if floor_only else max(4 * e32, FLOOR)
+        worst = max(worst, err / bar)
+        print(f"[arap {tag}] {k}: e32 {e32:.3e} kernel {err:.3e} bar {bar:.3e}")
+        if not err <= bar:
+            failures.append((k, e32, err, bar))
+    assert not failures, failures
+    return worst
+
+
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("name", sorted(arap_ref.SCENES))
 def test_energy_and_gradients_against_float64(name, weighted):
     scene = arap_ref.named_scene(name)                                                  # tests/test_arap_host.py checks the same scenes on the CPU
     r64, r32 = arap_ref.run(scene, torch.float64, weighted=weighted), arap_ref.run(scene, torch.float32, weighted=weighted)
-    assert torch.equal(r64["unchanged"], r32["unchanged"])                              # e32 below measures rounding only
     got, _ = _run_hip(scene, weighted)
     torch.cuda.synchronize()
     assert got["loss"].dim() == 0 and got["loss"].dtype == torch.float32 and got["R"].shape == r64["R"].shape
-    failures = []
-    for k in ("loss", "R", "d_targets", "d_source"):
-        e32, err = _rel(r32[k], r64[k]), _rel(got[k], r64[k])
-        bar = max(4 * e32, FLOOR)
-        print(f"[arap {name} w{int(weighted)}] {k}: e32 {e32:.3e} kernel {err:.3e} bar {bar:.3e}")
-        if not err <= bar:
-            failures.append((k, e32, err, bar))
-    assert not failures, failures
+    check_against_float64(f"{name} w{int(weighted)}", got, r64, r32)
     eye = torch.eye(3, device="cuda")
     assert torch.equal(got["R"][:2], eye.expand_as(got["R"][:2]))                       # the unchanged rule: exactly the identity
 

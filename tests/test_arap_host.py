@@ -160,3 +160,103 @@ def test_points_have_no_near_ties_so_float32_finds_the_float64_graph():
     assert torch.equal(idx32, idx64[:, :16])
     m32, m64 = arap_ref.mask_radius(idx32, dist32, 0.05), arap_ref.mask_radius(idx64[:, :16], dist64[:, :16], 0.05)
     assert torch.equal(m32[0], m64[0]) and int((m64[0] < 0).sum()) > 0 and int((m64[0][:, 3:] >= 0).sum()) > 0
+
+
+# ---- the scenes and clouds of tests/test_arap_edges_gpu.py: each terminates and holds the feature it is named for
+FLOOR = 16 * 2.0 ** -24
+
+
+def _inverse_entries(scene, v):
+    pairs = torch.cat([scene["sample_idx"][:, None], scene["nn_idx"][scene["sample_idx"]]], dim=1)
+    return int((pairs == v).sum())
+
+
+@pytest.mark.parametrize("name", sorted(arap_ref.EDGE_SCENES))
+def test_edge_scenes_terminate_and_hold_their_feature(name):
+    sc = arap_ref.named_scene(name)
+    src, tgt, nn, w, sidx = sc["source"], sc["targets"], sc["nn_idx"], sc["weight"], sc["sample_idx"]
+    Nv, K, (F, S) = src.shape[0], nn.shape[1], (tgt.shape[0], len(sidx))
+    assert 1 <= sc["rounds"] <= 5 and Nv <= 700 and S <= 300 and F <= 6
+    assert all(torch.equal(t.float().double(), t) for t in (src, tgt, w))                  # fp32 values
+    runs = {}
+    for weighted in (True, False):
+        r64, r32 = arap_ref.run(sc, torch.float64, weighted=weighted), arap_ref.run(sc, torch.float32, weighted=weighted)
+        assert torch.equal(r64["unchanged"], r32["unchanged"])
+        runs[weighted] = (r64, r32)
+    r64, r32 = runs[True]
+    un = r64["unchanged"]
+    if name not in arap_ref.RANK_ONE:                                                        # wherever R is compared with the oracle
+        assert float(arap_ref.worst_conditioning(src, tgt, nn, w, sidx).min()) >= arap_ref.COND
+    if name in arap_ref.RANK_ONE:
+        rank_one, closed = 0, 0.0
+        for f in range(F):
+            M, _, se, te, ws = arap_ref.covariances(src, tgt[f], nn, w, sidx)
+            sig = torch.linalg.svdvals(M)
+            rank_one += int(((sig[:, 0] > 0) & (sig[:, 1] <= 1e-12 * sig[:, 0])).sum())
+            closed += float((ws[:, 0] * (te[:, 0].norm(dim=-1) - se[:, 0].norm(dim=-1)) ** 2).sum())
+        assert K == 1 and rank_one == S * (F - 1) and bool(un[0].all()) and not bool(un[1:].any())
+        assert abs(float(r64["loss"]) - closed) <= 1e-12 * closed                           # R s^ = t^: the loss is sum w (|t| - |s|)^2
+        for k in ("loss", "d_targets", "d_source"):
+            assert _rel(r32[k], r64[k]) < 1e-5, k
+    elif name == "axes":
+        assert torch.equal(src * 4096.0, torch.round(src * 4096.0))
+        touch = torch.isin(torch.cat([sidx[:, None], nn[sidx]], dim=1), sc["marked"]).any(1)
+        assert bool(un[[0, 1, 3]].all()) and torch.equal(un[2], ~touch) and 0 < int(touch.sum()) < S
+        e_s, e_t = arap_ref.edges(src.float(), nn), arap_ref.edges(tgt[3].float(), nn)
+        assert torch.equal(e_s, e_t) and torch.equal(arap_ref.edges(src, nn), arap_ref.edges(tgt[3], nn))
+        assert not torch.equal(tgt[0][:, 0], src[:, 0]) and torch.equal(tgt[0][:, 1], src[:, 1]) and torch.equal(tgt[1][:, 2], src[:, 2])
+    elif name == "isolated":
+        iso = sc["isolated"]
+        assert bool((nn[iso] == -1).all()) and not bool(torch.isin(nn, iso).any()) and bool(torch.isin(iso, sidx).all())
+        assert torch.equal(sidx[sc["planted"]], iso) and float(w[nn < 0].min()) > 0.0 and int((nn[~torch.isin(torch.arange(Nv), iso)] < 0).sum()) > 0
+        assert torch.equal(sc["weight_masked"], w * (nn >= 0))
+    elif name == "diagonal":
+        seen = set()
+        for f in range(F):
+            M = arap_ref.covariances(src, tgt[f], nn, w, sidx)[0]
+            d = torch.diagonal(M, dim1=1, dim2=2)
+            assert torch.equal(torch.diag_embed(d), M)                                       # exactly diagonal: nothing for Jacobi to rotate
+            seen |= {(tuple(o), tuple(n)) for o, n in zip(d.abs().argsort(1).tolist(), (d < 0).tolist())}
+        assert len(seen) == 6 * 4 and not bool(un.any())                                     # six orderings x (none, x, y or z negative)
+        assert float((r64["R"] - sc["R_closed"]).abs().max()) <= 1e-12
+    elif name == "near_rigid":
+        e32 = _rel(r32["d_targets"], r64["d_targets"])
+        print(f"[arap scene near_rigid] d_targets: e32 {e32:.3e}, floor {FLOOR:.3e}")
+        assert e32 > 10 * FLOOR and not bool(un.any())                                       # the floor-only bar discriminates: fp32 inside fails it
+    elif name == "hub":
+        assert bool((nn[1:, 0] == 0).all()) and torch.equal(sidx, torch.arange(Nv).repeat(2)) and _inverse_entries(sc, 0) >= 2 * Nv
+    else:
+        want = {"k2": (600, 2, 129), "k16_radius": (700, 16, 257), "k5_nv255": (255, 5, 127), "k5_nv256": (256, 5, 127), "k5_nv257": (257, 5, 127)}
+        assert (Nv, K, S) == want[name] and bool(un[:2].all())
+        if name == "k16_radius":
+            assert 0.5 < float((nn < 0).double().mean()) < 0.9
+
+
+def test_lattice_and_tile_boundary_clouds_hold_their_ties():
+    pts = arap_ref.lattice_points()
+    assert pts.shape == (1331, 3) and torch.equal(pts * 16.0, torch.round(pts * 16.0)) and len(torch.unique(pts, dim=0)) == 1331
+    idx, dist = arap_ref.knn_exact(pts, 17)
+    assert torch.equal(dist * 256.0, torch.round(dist * 256.0))
+    assert torch.equal(arap_ref.knn_exact(pts.float(), 17)[1], dist)                         # exact in fp32 too
+    inner = int(torch.nonzero((pts.abs() <= 0.125).all(1))[0])
+    assert (dist[inner] * 256.0).tolist() == [1.0] * 6 + [2.0] * 11                          # the 6-fold shell, then the 12-fold one
+    for K in (1, 6, 7, 16):                                                                  # the cut falls inside a tie, in both tiles
+        tied = (dist == dist[:, K - 1:K]) & (torch.arange(17) >= K - 1)
+        assert int((tied.sum(1) > 1).sum()) > 0
+        assert int((tied & (idx < 1024)).sum()) > 0 and int((tied & (idx >= 1024)).sum()) > 0
+    r2 = arap_ref.LATTICE_RADIUS ** 2
+    assert r2 == 4.0 / 256.0 and int((dist[:, :16] == r2).sum()) > 0 and int((dist[:, 3:16] < r2).sum()) > 0
+    cut = arap_ref.mask_radius(idx[:, :16], dist[:, :16], arap_ref.LATTICE_RADIUS, 0)[0]
+    assert bool((cut[dist[:, :16] == r2] == -1).all()) and bool((cut[dist[:, :16] < r2] >= 0).all())
+    pts, idx, dist = arap_ref.tile_boundary_points()
+    assert pts.shape == (2049, 3) and torch.equal(pts[1023], pts[1024]) and torch.equal(pts.float().double(), pts)
+    assert idx[0, :3].tolist() == [1023, 1024, 2048] and float(dist[0, 0]) == float(dist[0, 1]) < float(dist[0, 2])
+    assert torch.equal(arap_ref.knn_exact(pts.float(), 18)[0], idx)
+
+
+def test_knn_exact_agrees_with_the_bruteforce_on_a_tie_free_cloud():
+    pts, _, idx, dist = arap_ref.make_points(1500, 16, 4, duplicates=0)
+    want_i, want_d = arap_ref.knn_exact(pts, 18)
+    assert torch.equal(want_i, idx) and torch.equal(want_d, dist)
+    pts, _, idx, dist = arap_ref.make_points(1025, 16, 2025, radius=0.119)                   # with the planted duplicates
+    assert torch.equal(arap_ref.knn_exact(pts, 18)[0], idx)

@@ -3,7 +3,7 @@ the widest access the kernels make through it, or an attention-backward do_scale
 A3D_EINVAL before anything reaches the GPU.  The device addresses below are made up and never dereferenced: every call differs from a
 valid launch in exactly one operand, and the argument checks run before the first HIP call, so this runs on a machine without a GPU.
 (No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)  The forward attention entry
-points and the deformation field's (a3d_dg_*) are held to the same discipline further down."""
+points, the deformation field's (a3d_dg_*) and the ARAP loss's (a3d_knn_f32, a3d_arap_*) are held to the same discipline further down."""
 import ctypes
 import math
 
@@ -335,3 +335,76 @@ def test_gemm_family_ws_query_with_invalid_flags(lib, entry, f16):
         need = ctypes.c_int64(-1)
         assert _gemm_call(lib, entry, f16, ws_needed=need, flags=flags) == 0, f"{entry}: flags {flags:#x}"
         assert need.value == 0, f"{entry}: flags {flags:#x} -> {need.value} bytes"
+
+
+# ---- ARAP loss and its k-NN graph (a3d_knn_f32, a3d_arap_*_f32, csrc/arap.hip): fp32 only, one build
+KNN_OPERANDS = ("points", "nn_idx", "nn_dist")
+KNN_VALID = dict(N=300, K=3, least=3)
+ARAP_VALID = dict(F=4, Nv=300, K=3, S=64, bs=900)
+ARAP_HEAD = ("source", "targets", "nn_idx", "weight", "sample_idx")
+ARAP_OPERANDS = {
+    "a3d_arap_energy_f32": ARAP_HEAD + ("rot", "rot_f32", "energy", "loss"),
+    "a3d_arap_backward_f32": ARAP_HEAD + ("rot", "order", "starts", "grad_out", "d_targets", "d_source"),
+}
+ARAP_ALIGN8 = ("rot", "energy")                                  # fp64: the rotations and the per-sample energies
+# weight, rot_f32, grad_out and d_source may be NULL (unit weights, no fp32 copy of R, zero gradients, no source gradient): with every
+# other operand valid such a call would launch, so none is made here.
+ARAP_OPTIONAL = ("weight", "rot_f32", "grad_out", "d_source")
+
+
+def _knn_call(lib, ptr=None, **geometry):
+    """The valid search (300 points, K = 3) with the named pointers / geometry words replaced.  Callers replace exactly one, and never none."""
+    assert ptr or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(KNN_OPERANDS)
+    p.update(ptr or {})
+    g = dict(KNN_VALID, **geometry)
+    return lib.a3d_knn_f32(None, g["N"], p["points"], g["K"], g["least"], 0.01, p["nn_idx"], p["nn_dist"])
+
+
+def _arap_call(lib, entry, ptr=None, **geometry):
+    """The valid launch of `entry` (F = 4, Nv = 300, K = 3, S = 64, dense frames) with the named pointers / geometry words replaced."""
+    assert ptr or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(ARAP_OPERANDS[entry])
+    p.update(ptr or {})
+    g = dict(ARAP_VALID, **geometry)
+    head = [None, g["F"], g["Nv"], g["K"], g["S"], p["source"], p["targets"], g["bs"], p["nn_idx"], p["weight"], p["sample_idx"]]
+    return getattr(lib, entry)(*head, *[p[n] for n in ARAP_OPERANDS[entry][5:]])
+
+
+def test_knn_refusals(lib):
+    """No points, a missing or misaligned operand and a negative least_edge_num are A3D_EINVAL; a K without a kernel (the list lengths are
+    1 ... 16) is A3D_EUNSUPPORTED; fewer than K other points is A3D_EINVAL."""
+    base = _ptrs(KNN_OPERANDS)
+    for operand in KNN_OPERANDS:
+        assert _knn_call(lib, ptr={operand: None}) == A3D_EINVAL, f"NULL {operand}"
+        assert _knn_call(lib, ptr={operand: base[operand] + 2}) == A3D_EINVAL, f"{operand} at +2 bytes"
+    for g in (dict(N=0), dict(N=-1), dict(least=-1), dict(N=3), dict(N=2), dict(N=16, K=16)):
+        assert _knn_call(lib, **g) == A3D_EINVAL, g
+    for K in (0, 17, -1):
+        assert _knn_call(lib, K=K) == A3D_EUNSUPPORTED, K
+
+
+ARAP = pytest.mark.parametrize("entry", sorted(ARAP_OPERANDS))
+
+
+@ARAP
+def test_arap_refuses_misaligned_or_missing_operand(lib, entry):
+    """Every required operand NULL; rot / energy 4 bytes off their 8-byte alignment; every 4-byte operand 2 bytes off."""
+    base = _ptrs(ARAP_OPERANDS[entry])
+    for operand in ARAP_OPERANDS[entry]:
+        off = 4 if operand in ARAP_ALIGN8 else 2
+        rc = _arap_call(lib, entry, ptr={operand: base[operand] + off})
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +{off} bytes returned {rc}"
+        if operand not in ARAP_OPTIONAL:
+            rc = _arap_call(lib, entry, ptr={operand: None})
+            assert rc == A3D_EINVAL, f"{entry}: NULL {operand} returned {rc}"
+
+
+@ARAP
+def test_arap_refuses_bad_geometry(lib, entry):
+    """Empty extents, a negative batch stride, F beyond a grid's y extent (the backward launches F + 1 rows), and the 32-bit limits:
+    F S <= 2^28 (frame, sample) pairs, S (K + 1) <= 2^30 inverse-list entries."""
+    bad = [{k: v} for k in ("F", "Nv", "K", "S") for v in (0, -1)]
+    bad += [dict(bs=-1), dict(F=65535), dict(F=16385, S=16384), dict(F=1, S=2 ** 28, K=4)]
+    for g in bad:
+        assert _arap_call(lib, entry, **g) == A3D_EINVAL, f"{entry}: {g}"
