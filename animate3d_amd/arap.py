@@ -42,6 +42,23 @@ Host synchronisation: nothing in ``arap_energy``'s forward or backward synchroni
 ``nonzero``, no data-dependent shape: out-of-range indices are handled in the kernels (such an edge is absent, such a sample contributes
 nothing).  The step stays capturable.  (The drop-in ``cal_connectivity_from_points`` returns the reference's masked edge list, whose
 length depends on the data: it synchronises, once per graph.)
+
+The mesh branch (animate3d.py:222-234, ``connected_vertices_info_path``; ``configs/mesh_animation_frame_16.yaml``)
+
+``MeshGraph`` holds a mesh's fixed, directed vertex adjacency in CSR form on the device (``row_start [Nv + 1]``, ``col [E]``, int32) and
+``MeshGraph.sample(K)`` draws every step's ``nn_idx [Nv, K]`` from it in one launch of ``a3d_mesh_sample_neighbours``, where the
+reference's ``sample_matrix_vectorized`` (util.py:320-344) makes a ``rand(Nv, Dmax)``, a masked add, a full sort along ``Dmax`` and an
+advanced-index gather.  The sampling contract: for vertex v of degree d the row holds ``min(K, d)`` distinct positions of its adjacency
+row, a uniformly random subset, in ascending row position, then -1; a row with ``d <= K`` holds all its neighbours, one with ``d = 0`` is
+all -1.  The draw is a pure function of ``(seed, v)`` and the graph (selection sampling on Philox4x32-10; specified to the bit in
+include/animate3d_hip.h), so it does not depend on the launch geometry and a host restatement is bit-exact.
+
+Subset against tuple.  The reference's row is the first P columns of a random permutation of the d neighbours: a uniformly random
+*ordered* P-tuple without repetition, followed by -1 where ``d < P`` (its -1 column index picks the padded last column; defined for
+``P <= Dmax``).  Ours is the same tuple's *set*, listed in row order.  The set of a uniform ordered tuple is a uniform subset, and the
+only consumer, ``cal_arap_error`` as ``training_step`` calls it (animate3d.py:241: no ``weight``), sums unit-weight terms over k, both in
+the covariance ``S`` and in the energy: the column order changes nothing but the order of an fp64 summation.  Sampling is per vertex, not
+per ``sample_idx`` entry: duplicated entries of ``sample_idx`` see the same row, as in the reference.
 """
 from __future__ import annotations
 
@@ -99,7 +116,8 @@ class ArapGraph(TensorKeyed):
     @classmethod
     def from_neighbours(cls, xyz: torch.Tensor, nn_idx: torch.Tensor, nn_dist: Optional[torch.Tensor] = None, radius: Optional[float] = None,
                         least_edge_num: int = 3) -> "ArapGraph":
-        """A graph that was found elsewhere (a mesh's connectivity: a dense ``nn_idx`` with -1 entries), under the same key."""
+        """A graph that was found elsewhere (a fixed dense ``nn_idx`` with -1 entries), under the same key.  A mesh's connectivity, whose
+        neighbours are drawn again every step, is a ``MeshGraph``."""
         return cls(xyz, nn_idx.shape[1], radius, least_edge_num, neighbours=(nn_idx, nn_dist))
 
     def matches(self, xyz: torch.Tensor) -> bool:
@@ -109,6 +127,114 @@ class ArapGraph(TensorKeyed):
         if not self.matches(xyz):
             self._bind(xyz)
         return self
+
+
+def _check_sample_k(K: int):
+    if not 1 <= int(K) <= K_MAX:
+        raise NotImplementedError(f"K = {K}: the sampling kernel supports 1 <= K <= {K_MAX}")
+
+
+class MeshGraph:
+    """A mesh's fixed, directed vertex adjacency in CSR form: ``row_start [Nv + 1]`` and ``col [E]`` int32 on one device; row v is
+    ``col[row_start[v]:row_start[v + 1]]`` in the order it was given.  ``Nv``, ``max_degree`` and ``degrees [Nv]`` describe it.  The
+    constructors run once per stage and may synchronise with the host; ``sample`` runs every step and does not.  See the module
+    docstring for the sampling contract."""
+
+    def __init__(self, row_start: torch.Tensor, col: torch.Tensor, max_degree: Optional[int] = None):
+        if row_start.dim() != 1 or row_start.shape[0] < 2 or col.dim() != 1 or row_start.device != col.device:
+            raise ValueError("expected row_start [Nv + 1] and col [E] on one device")
+        self.row_start, self.col = row_start.to(torch.int32).contiguous(), col.to(torch.int32).contiguous()
+        self.Nv = self.row_start.shape[0] - 1
+        self.degrees = self.row_start[1:] - self.row_start[:-1]
+        self.max_degree = int(self.degrees.max()) if max_degree is None else int(max_degree)
+
+    @property
+    def device(self) -> torch.device:
+        return self.row_start.device
+
+    @classmethod
+    def _from_degrees(cls, degrees: torch.Tensor, col: torch.Tensor) -> "MeshGraph":
+        Nv = degrees.shape[0]
+        if Nv < 1:
+            raise ValueError("a mesh graph needs at least one vertex")
+        if col.numel() >= 2 ** 31:
+            raise ValueError(f"{col.numel()} edges: the adjacency is indexed in 32 bits")
+        if col.numel() and (int(col.min()) < 0 or int(col.max()) >= Nv):
+            raise IndexError(f"neighbour indices must lie in [0, {Nv}), got [{int(col.min())}, {int(col.max())}]")
+        row_start = torch.zeros(Nv + 1, dtype=torch.int64, device=degrees.device)
+        row_start[1:] = torch.cumsum(degrees.long(), 0)
+        return cls(row_start, col)
+
+    @classmethod
+    def from_connected_vertices(cls, info, device="cuda") -> "MeshGraph":
+        """From the parsed JSON of ``connected_vertices_info_path``: ``{str(v): {str(u): anything, ...}, ...}`` with every vertex
+        ``0 .. Nv - 1`` a key (``ValueError`` otherwise).  The neighbours of v are ``info[str(v)].keys()`` in dict order, as
+        util.py:313-315 reads them; one outside ``[0, Nv)`` raises ``IndexError``."""
+        Nv = len(info)
+        rows = []
+        for v in range(Nv):
+            if str(v) not in info:
+                raise ValueError(f"connected vertices: vertex {v} of {Nv} is not a key")
+            rows.append([int(u) for u in info[str(v)].keys()])
+        degrees = torch.tensor([len(r) for r in rows], dtype=torch.int64)
+        col = torch.tensor([u for r in rows for u in r], dtype=torch.int64)
+        return cls._from_degrees(degrees.to(device), col.to(device))
+
+    @classmethod
+    def from_padded(cls, nn_idx: torch.Tensor, mask: Optional[torch.Tensor] = None) -> "MeshGraph":
+        """From a dense ``nn_idx [Nv, D]`` with -1 padding, the reference's in-memory form (``mask``: its ``max_idx``, by default
+        ``nn_idx != -1``).  The -1 entries may sit anywhere in a row; the others keep their order.  Duplicates in a row are kept: they
+        are drawn as the distinct positions they are, so a duplicated neighbour can appear twice in a sampled row, with twice the
+        weight in the energy.  The caller owns them."""
+        if nn_idx.dim() != 2 or nn_idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"nn_idx: expected an int32 / int64 [Nv, D], got {nn_idx.dtype} {tuple(nn_idx.shape)}")
+        mask = nn_idx != -1 if mask is None else mask.to(nn_idx.device).bool()
+        if mask.shape != nn_idx.shape:
+            raise ValueError(f"mask: expected {tuple(nn_idx.shape)}, got {tuple(mask.shape)}")
+        return cls._from_degrees(mask.sum(1), nn_idx[mask].long())            # boolean indexing is row-major: each row keeps its order
+
+    @classmethod
+    def from_faces(cls, faces: torch.Tensor, Nv: int) -> "MeshGraph":
+        """The undirected vertex adjacency of the triangles ``faces [F, 3]``: both directions of every edge, once each however many faces
+        (or repeated faces) share it, every row ascending.  A degenerate face's repeated corner contributes no self-edge.  Torch ops on
+        the device ``faces`` is on; an index outside ``[0, Nv)`` raises ``IndexError``."""
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"faces: expected an int32 / int64 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+        Nv = int(Nv)
+        f = faces.long()
+        if f.numel() and (int(f.min()) < 0 or int(f.max()) >= Nv):
+            raise IndexError(f"faces: vertex indices must lie in [0, {Nv}), got [{int(f.min())}, {int(f.max())}]")
+        a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
+        b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+        a, b = torch.cat([a, b]), torch.cat([b, a])
+        keys = torch.unique((a * Nv + b)[a != b])                             # sorted: by vertex, then by neighbour
+        src = torch.div(keys, Nv, rounding_mode="floor")
+        return cls._from_degrees(torch.bincount(src, minlength=Nv), keys - src * Nv)
+
+    def padded(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(nn_idx [Nv, max_degree] int64 with -1 padding, max_idx bool): what ``prepare_arap_from_mesh_vertices`` returns."""
+        slot = torch.arange(self.max_degree, device=self.device)[None]
+        max_idx = slot < self.degrees[:, None]
+        nn_idx = torch.full((self.Nv, self.max_degree), -1, dtype=torch.int64, device=self.device)
+        nn_idx[max_idx] = self.col.long()
+        return nn_idx, max_idx
+
+    def sample(self, K: int, *, generator: Optional[torch.Generator] = None, seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step's neighbours: ``nn_idx [Nv, K]`` int32 under the module docstring's contract.  ``seed`` is a ``[1]`` int64 CUDA tensor,
+        read on the device; by default ``torch.randint(0, 2**62, (1,), dtype=int64, generator=generator, device=dev)``: one draw from the
+        generator, no ``.item()``.  One kernel launch, no host synchronisation, no ``Nv x max_degree`` temporary."""
+        _check_sample_k(K)
+        require_index_cuda("row_start", self.row_start)
+        dev = self.device
+        if seed is None:
+            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=generator, device=dev)
+        elif not (isinstance(seed, torch.Tensor) and seed.is_cuda and seed.dtype == torch.int64 and tuple(seed.shape) == (1,)):
+            raise ValueError("seed: a [1] int64 CUDA tensor (it is read on the device)")
+        elif seed.device != dev:
+            raise ValueError(f"seed is on {seed.device}, the graph on {dev}")
+        nn_idx = torch.empty(self.Nv, int(K), dtype=torch.int32, device=dev)
+        launch("a3d_mesh_sample_neighbours", dev, self.Nv, self.col.shape[0], _p(self.row_start), _p(self.col), int(K), _p(seed), _p(nn_idx))
+        return nn_idx
 
 
 def inverse_list(sample_idx: torch.Tensor, nn_idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -266,3 +392,18 @@ def cal_arap_error(nodes_sequence, ii, jj, nn, K=10, weight=None, sample_num=512
     nn_idx = edges_to_dense(ii, jj, nn, Nv, K)
     return arap_energy(nodes_sequence[0], nodes_sequence[1:], nn_idx, weight=weight, sample_idx=sample_idx, sample_num=sample_num,
                        generator=generator, return_rotations=return_rotations)
+
+
+def prepare_arap_from_mesh_vertices(connected_vertices_info, device="cpu"):
+    """Drop-in for util.py:300-318: (nn_idx [Nv, Dmax] int64 with -1 padding, max_idx bool), on the CPU as the reference returns them
+    (``device`` is an addition).  ``training_step`` wants the ``MeshGraph`` itself: ``MeshGraph.from_connected_vertices(info)``."""
+    return MeshGraph.from_connected_vertices(connected_vertices_info, device).padded()
+
+
+def sample_matrix_vectorized(input_matrix, P, max_index, *, generator=None, seed=None):
+    """Drop-in for util.py:320-344: ``input_matrix [N, Dmax]`` and its mask ``max_index`` -> int64 ``[N, P]`` under ``MeshGraph.sample``'s
+    contract (a random subset in row order where the reference gives a random tuple; the module docstring says why that is
+    equivalent).  The keyword-only arguments are additions.  This builds a ``MeshGraph.from_padded`` on every call, which synchronises
+    with the host: a caller in a loop should hold the ``MeshGraph`` and call ``sample``."""
+    require_index_cuda("input_matrix", input_matrix)
+    return MeshGraph.from_padded(input_matrix, max_index).sample(P, generator=generator, seed=seed).long()

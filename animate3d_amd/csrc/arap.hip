@@ -14,7 +14,11 @@
 //   arap_reduce_kernel   the F * S energies summed in a fixed order by one block
 //   arap_bwd_kernel      gather form: one thread per (frame, vertex) walks the vertex's entries of the inverse list (sorted (sample, slot)
 //                        pairs: slot 0 the sample's centre, slot k + 1 its k-th neighbour); no atomics, rows without entries are written 0
-#include "common.h"
+//   mesh_sample_kernel   the mesh branch's per-step neighbour draw (sample_matrix_vectorized, util.py:320-344: rand + masked add + sort +
+//                        gather over [Nv, Dmax]): one thread per vertex walks its CSR row once and keeps K of its d positions by selection
+//                        sampling (Knuth's Algorithm S) on Philox4x32-10 words keyed by (seed, vertex, position).  Integers only, no LDS,
+//                        no per-thread array, nothing that depends on a maximum degree or on the launch geometry
+#include "f32_common.h"
 
 #ifndef A3D_STORAGE_F16
 #include <math.h>
@@ -337,6 +341,49 @@ __global__ __launch_bounds__(KNN_BLOCK) void arap_bwd_kernel(ArapArgs a, const d
   }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11), as Random123 specifies it: ten rounds of
+//   (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),
+// the key raised by (W0, W1) between rounds.
+A3D_DEV void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c[4]) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0], hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
+// Row v of nn_idx: min(K, d) of the d entries col[row_start[v] ...] in ascending position, a uniformly random subset, then -1.
+// Position p is kept iff mulhi32(r_p, d - p) < K - kept (so always while as many are needed as are left: a row with d <= K is copied);
+// r_p is word p % 4 of the Philox block with key (seed lo, seed hi) and counter (v, p / 4, 0, 0).  A row_start outside [0, E] or
+// descending is clamped: such a row is short, never out of bounds.
+__global__ __launch_bounds__(256) void mesh_sample_kernel(int Nv, int E, const int* __restrict__ row_start, const int* __restrict__ col, int K,
+                                                          const int64_t* __restrict__ seed, int* __restrict__ nn_idx) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= Nv) return;
+  const int b = max(0, min(row_start[v], E)), e = max(b, min(row_start[v + 1], E));
+  const int d = e - b;
+  const uint64_t s = (uint64_t)seed[0];
+  const uint32_t k0 = (uint32_t)s, k1 = (uint32_t)(s >> 32);
+  int* out = nn_idx + (int64_t)v * K;
+  int kept = 0;
+  for (int q = 0; 4 * q < d && kept < K; ++q) {
+    uint32_t r[4] = {(uint32_t)v, (uint32_t)q, 0u, 0u};
+    if (d > K) philox4x32_10(k0, k1, r);               // a row that is copied whole draws nothing
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int p = 4 * q + j;
+      if (p < d && kept < K && (d <= K || __umulhi(r[j], (uint32_t)(d - p)) < (uint32_t)(K - kept))) out[kept++] = col[b + p];
+    }
+  }
+  for (; kept < K; ++kept) out[kept] = -1;
+}
+
 template <int K>
 void knn_launch(hipStream_t st, int N, const float* pts, int Kout, int least, float r2, int* nn_idx, float* nn_dist) {
   knn_kernel<K><<<(N + KNN_BLOCK - 1) / KNN_BLOCK, KNN_BLOCK, 0, st>>>(N, pts, Kout, least, r2, nn_idx, nn_dist);
@@ -395,6 +442,15 @@ extern "C" int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, 
     return A3D_EINVAL;
   const dim3 grid((Nv + KNN_BLOCK - 1) / KNN_BLOCK, F + (d_source ? 1 : 0));
   arap_bwd_kernel<<<grid, KNN_BLOCK, 0, (hipStream_t)stream>>>(a, rot, order, starts, grad_out, d_targets, d_source);
+  return a3d_launch_status();
+}
+
+extern "C" int a3d_mesh_sample_neighbours(a3d_stream_t stream, int Nv, int E, const int* row_start, const int* col, int K, const int64_t* seed,
+                                          int* nn_idx) {
+  if (Nv < 1 || E < 0 || !row_start || (!col && E > 0) || !seed || !nn_idx) return A3D_EINVAL;
+  if (!a3d_aligned(4, row_start, col, nn_idx) || !a3d_aligned(8, seed)) return A3D_EINVAL;
+  if (K < 1 || K > 16) return A3D_EUNSUPPORTED;
+  mesh_sample_kernel<<<blocks_for(Nv), 256, 0, (hipStream_t)stream>>>(Nv, E, row_start, col, K, seed, nn_idx);
   return a3d_launch_status();
 }
 

@@ -1,6 +1,6 @@
-// Shared by the fp32 4-D stage (splat.hip, deform4d.hip): the grid-size helper and the one reduction their atomic-free backward passes have
+// Shared by the fp32 4-D stage (splat.hip, deform4d.hip, arap.hip): the grid-size helper and the one reduction their atomic-free backward passes have
 // in common.  Math helpers stay in their files: two spellings of one formula round differently.  A file that includes this gets the kernel
-// in its code object, so only files that launch it do.
+// in its code object, so only files that launch it do; arap.hip takes blocks_for from here and carries the kernel unlaunched.
 #pragma once
 #include "common.h"
 

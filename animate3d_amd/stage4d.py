@@ -25,17 +25,18 @@ is no torch fallback.
   gradient is read on the device: neither direction synchronises with the host.  Without a gradient to compute nothing is saved.
 
 ``sampled_frames`` / ``sampled_image_index`` restate the progressive frame schedule (animate3d.py:134-157); ``render_batch`` is the
-renderer for a whole batch with the policy of advanced_4d.py:130-162; ``training_step`` is the step; ``field_param_groups`` the
-optimiser groups of geometry/gaussian_4d.py:344-391.
+renderer for a whole batch with the policy of advanced_4d.py:130-162; ``training_step`` is the step, with either ARAP branch (the k-NN
+graph or the mesh's connectivity); ``vertex_trajectory`` the deformed means of every frame (``save_gaussian_trajectory``);
+``field_param_groups`` the optimiser groups of geometry/gaussian_4d.py:344-391.
 """
 from __future__ import annotations
 
 import random
-from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from .arap import ArapGraph, arap_energy
+from .arap import ArapGraph, MeshGraph, arap_energy
 from .deform4d import HexPlaneDeformation
 from .f32_stage import launch, require_f32_cuda, require_index_cuda
 from .hip_ops import _p
@@ -238,7 +239,7 @@ def render_batch(field: HexPlaneDeformation, gaussians: Gaussians, c2w: torch.Te
 # ---- the step (animate3d.py:120-370)
 
 def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict, *, loss: Dict[str, float], global_step: int, n_view: int,
-                  n_frame: int, progressive_iter_per_frame: int, bg, graph: Optional[ArapGraph] = None,
+                  n_frame: int, progressive_iter_per_frame: int, bg, graph: Optional[Union[ArapGraph, MeshGraph]] = None,
                   guidance: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, sample_strategy: str = "normal",
                   first_frame_trainable: bool = False, keep_prob: float = 0.1, generator: Optional[torch.Generator] = None, rng=random,
                   render: Callable[..., Dict] = render_batch) -> Dict[str, torch.Tensor]:
@@ -248,8 +249,16 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     [., H, W, 1]`` bool, ``c2w``, ``fovy``, ``timestamps``) and, for a guidance step, ``random_camera`` (``c2w``, ``fovy``, ``timestamps``,
     ``height``, ``width``).  ``guidance``: ``comp_rgb [B, H, W, 3] -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound); a step with a
     guidance callable is the reference's ``load_guidance: true``.  ``loss``: the lambdas under the reference's names (``lambda_rgb``,
-    ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num``); a non-zero value for one this module does not build raises
-    ``NotImplementedError``.  ``bg``: the three background values.  ``render`` is ``render_batch``'s stand-in for tests.
+    ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num`` and, for the mesh branch, ``arap_K``); a non-zero value for one
+    this module does not build raises ``NotImplementedError``.  ``bg``: the three background values.  ``render`` is ``render_batch``'s
+    stand-in for tests.
+
+    ``graph`` chooses the branch of animate3d.py:222-239.  An ``ArapGraph`` is the k-NN graph of ``xyz``, fixed for the stage.  A
+    ``MeshGraph`` is the mesh's connectivity (``connected_vertices_info_path``): every step draws ``arap_K`` of each vertex's neighbours
+    with ``graph.sample`` (``graph.Nv`` must be the number of Gaussians and ``loss["arap_K"]`` must be there: ``ValueError``, raised
+    before anything touches a device).  Draws from ``generator`` within a step, in the reference's order (:224, then :241): the
+    renders' keep-masks, then with a ``MeshGraph`` the sampler's seed (one int64), then ``arap_energy``'s ``sample_idx``.  With an
+    ``ArapGraph`` the step draws exactly what it drew before the mesh branch existed.
 
     In the reference's order: the schedule and the ``(view, frame)`` index; one render of the gathered cameras and the masked RGB / mask
     MSE against ``rgb`` / ``mask`` read through the index; with guidance a render of the random cameras and ``lambda_sds * guidance(comp_rgb)``
@@ -262,7 +271,12 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     do_guidance = guidance is not None
     lambda_arap = float(loss.get("lambda_arap", 0.0))
     if lambda_arap > 0.0 and graph is None:
-        raise ValueError("lambda_arap > 0 needs graph=ArapGraph(xyz, K=arap_K, radius=arap_radius)")
+        raise ValueError("lambda_arap > 0 needs graph=ArapGraph(xyz, K=arap_K, radius=arap_radius) or a MeshGraph")
+    if lambda_arap > 0.0 and isinstance(graph, MeshGraph):
+        if graph.Nv != gaussians.xyz.shape[0]:
+            raise ValueError(f"graph: a mesh of {graph.Nv} vertices for {gaussians.xyz.shape[0]} Gaussians")
+        if "arap_K" not in loss:
+            raise ValueError("a MeshGraph needs loss['arap_K']: the number of neighbours drawn per vertex and step")
     rgb, mask = batch["rgb"], batch["mask"]
     if rgb.shape[0] != n_view * n_frame:
         raise ValueError(f"batch['rgb']: expected {n_view * n_frame} images (n_view * n_frame), got {rgb.shape[0]}")
@@ -283,11 +297,29 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
         total = total + loss_sds
         terms["loss_sds"] = loss_sds.detach()
     if lambda_arap > 0.0:
-        loss_arap = lambda_arap * arap_energy(gaussians.xyz, out["means3D"][:len(frames)], graph.refresh(gaussians.xyz).nn_idx,
+        if isinstance(graph, MeshGraph):
+            nn_idx = graph.sample(int(loss["arap_K"]), generator=generator)
+        else:
+            nn_idx = graph.refresh(gaussians.xyz).nn_idx
+        loss_arap = lambda_arap * arap_energy(gaussians.xyz, out["means3D"][:len(frames)], nn_idx,
                                               sample_num=int(loss.get("arap_sample_num", 512)), generator=generator)
         total = total + loss_arap
         terms["loss_arap"] = loss_arap.detach()
     return {"loss": total, **terms}
+
+
+def vertex_trajectory(field: HexPlaneDeformation, gaussians: Gaussians, timestamps: torch.Tensor) -> torch.Tensor:
+    """The deformed means of every frame, ``[T, N, 3]`` for ``timestamps [T]`` (frame t at ``timestamps[t]``, in the order given), in one
+    deformation call without a graph for autograd.  The reference's ``save_gaussian_trajectory`` writes ``mesh_trajectory/{i}.npy`` from
+    ``out["means3D"][0]`` of one render per frame (animate3d.py:465-471); row i of this is that array.  The scales are not deformed: the
+    means do not depend on them.  No file is written here."""
+    require_f32_cuda("timestamps", timestamps)
+    if timestamps.dim() != 1:
+        raise ValueError(f"timestamps: expected [T], got {tuple(timestamps.shape)}")
+    g = gaussians
+    with torch.no_grad():
+        means, _, _ = field(g.xyz, g.scaling, g.rotation, timestamps.float().contiguous(), None, deform_scales=False)
+    return means
 
 
 def field_param_groups(field: HexPlaneDeformation, *, delta_xyz_network_lr: float, delta_rot_network_lr: float,

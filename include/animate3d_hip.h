@@ -469,7 +469,21 @@ int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, const float* x
  *   a3d_arap_backward_f32  order [S (K + 1)] / starts [Nv + 1]: the (sample, slot) pairs s (K + 1) + c (slot 0: the sample's vertex, slot k + 1
  *                          its k-th neighbour) stable-sorted by vertex, absent ones last, and each vertex's first position; grad_out [1]
  *                          or NULL (zero); d_targets [F, Nv, 3] contiguous, d_source [Nv, 3] or NULL.  The rotations are constants.  No
- *                          atomics: each vertex sums its entries in list order, frames ascending; rows without entries are written 0 */
+ *                          atomics: each vertex sums its entries in list order, frames ascending; rows without entries are written 0
+ *   a3d_mesh_sample_neighbours  the mesh branch's per-step draw (sample_matrix_vectorized, util.py:320-344) over a fixed CSR adjacency:
+ *                          row_start [Nv + 1] and col [E] int32 (col may be NULL when E = 0), seed [1] int64 read on the device, nn_idx
+ *                          [Nv, K] int32 out.  Row v has d = row_start[v + 1] - row_start[v] entries (bounds outside [0, E] or descending
+ *                          are clamped: a short row, never an access out of bounds).  Its positions p = 0 .. d - 1 are walked once;
+ *                          position p is kept iff mulhi32(r_p, d - p) < K - kept, where mulhi32 is the high word of the 32 x 32-bit
+ *                          product and kept counts the positions kept so far (selection sampling, Knuth's Algorithm S: a uniformly
+ *                          random subset of min(K, d) positions, in ascending position; bias at most d / 2^32 per decision);
+ *                          nn_idx[v, kept] = col[row_start[v] + p]; the walk ends at kept = K; the rest of the row is -1.  A row with
+ *                          d <= K is copied whole.  r_p is word p % 4 of Philox4x32-10 (Salmon et al. 2011, as in Random123: multipliers
+ *                          0xD2511F53 on word 0 and 0xCD9E8D57 on word 2, key increments 0x9E3779B9 and 0xBB67AE85, round
+ *                          (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), the key raised between
+ *                          rounds) with key (low, high 32 bits of seed[0]) and counter (v, p / 4, 0, 0): a row depends on (seed, v) and
+ *                          the graph alone.  Nv >= 1, E >= 0; pointers 4-byte aligned, seed 8-byte aligned (else A3D_EINVAL);
+ *                          1 <= K <= 16 (else A3D_EUNSUPPORTED).  One launch, one thread per vertex, no workspace */
 int a3d_knn_f32(a3d_stream_t stream, int N, const float* points, int K, int least_edge_num, float radius2, int* nn_idx, float* nn_dist);
 int a3d_arap_energy_f32(a3d_stream_t stream, int F, int Nv, int K, int S, const float* source, const float* targets, int64_t targets_bs,
                         const int* nn_idx, const float* weight, const int* sample_idx, double* rot, float* rot_f32, double* energy,
@@ -477,6 +491,8 @@ int a3d_arap_energy_f32(a3d_stream_t stream, int F, int Nv, int K, int S, const 
 int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, int S, const float* source, const float* targets, int64_t targets_bs,
                           const int* nn_idx, const float* weight, const int* sample_idx, const double* rot, const int* order,
                           const int* starts, const float* grad_out, float* d_targets, float* d_source);
+int a3d_mesh_sample_neighbours(a3d_stream_t stream, int Nv, int E, const int* row_start, const int* col, int K, const int64_t* seed,
+                               int* nn_idx);
 
 /* Reconstruction loss of the 4-D stage (csrc/recon_loss.hip; contract in animate3d_amd/stage4d.py, masked_recon_loss), fp32.  Replaces the
  * val[sampled_idx] copies, the mask compositing and the two F.mse_loss of custom/threestudio-animate3d/systems/animate3d.py:160-184 and the
