@@ -605,14 +605,19 @@ __global__ __launch_bounds__(256) void gs_preprocess_bwd_kernel(GsInputs in, con
   d_opac[idx] = vis ? g[5] : 0.f;
 }
 
+// extents shared by duplicate / render / render_bwd: B N Gaussians and B * tiles ranges are indexed in 32 bits
+inline bool gs_extents_ok(int B, int N, int H, int W) {
+  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || (int64_t)B * N > 0x7fffffffLL) return false;
+  const int64_t gx = ((int64_t)W + GS_TILE - 1) / GS_TILE, gy = ((int64_t)H + GS_TILE - 1) / GS_TILE;
+  return gx * gy <= 0x7fffffffLL / B;
+}
+
 inline bool gs_inputs_ok(const GsInputs& in) {
-  if (in.B <= 0 || in.N <= 0 || in.H <= 0 || in.W <= 0 || (int64_t)in.B * in.N > 0x7fffffffLL) return false;
+  if (!gs_extents_ok(in.B, in.N, in.H, in.W)) return false;
   if (!in.means || !in.scales || !in.rots || !in.opac || !in.view || !in.proj || !in.campos || !in.tanfovx || !in.tanfovy) return false;
   if ((in.shs == nullptr) == (in.colors == nullptr)) return false;                 // exactly one colour source
   if (in.shs && (in.deg < 0 || in.deg > 3 || in.M < (in.deg + 1) * (in.deg + 1))) return false;
-  const int64_t gx = (in.W + GS_TILE - 1) / GS_TILE, gy = (in.H + GS_TILE - 1) / GS_TILE;
-  if ((int64_t)in.B * gx * gy > 0x7fffffffLL) return false;
-  return true;
+  return a3d_aligned(4, in.means, in.scales, in.rots, in.opac, in.shs, in.colors, in.view, in.proj, in.campos, in.tanfovx, in.tanfovy);
 }
 
 GsInputs make_inputs(int B, int N, const float* means, int64_t means_bs, const float* scales, int64_t scales_bs, const float* rots,
@@ -641,7 +646,7 @@ extern "C" int a3d_gs_preprocess_f32(a3d_stream_t stream, A3D_GS_INPUT_PARAMS, i
                                      float* rgb, int* clamped, int* tiles_touched) {
   const GsInputs in = make_inputs(A3D_GS_INPUT_ARGS);
   if (!gs_inputs_ok(in) || !radii || !xy || !depth || !conic_o || !rgb || !clamped || !tiles_touched) return A3D_EINVAL;
-  if (!a3d_aligned(16, conic_o) || !a3d_aligned(8, xy)) return A3D_EINVAL;
+  if (!a3d_aligned(16, conic_o) || !a3d_aligned(8, xy) || !a3d_aligned(4, radii, depth, rgb, clamped, tiles_touched)) return A3D_EINVAL;
   gs_preprocess_kernel<<<blocks_for((int64_t)B * N), 256, 0, (hipStream_t)stream>>>(in, radii, reinterpret_cast<float2*>(xy), depth,
                                                                                      reinterpret_cast<float4*>(conic_o), rgb, clamped, tiles_touched);
   return a3d_launch_status();
@@ -649,14 +654,16 @@ extern "C" int a3d_gs_preprocess_f32(a3d_stream_t stream, A3D_GS_INPUT_PARAMS, i
 
 extern "C" int a3d_gs_duplicate_f32(a3d_stream_t stream, int B, int N, int H, int W, const float* xy, const float* depth, const int* radii,
                                     const int64_t* offsets, int64_t* keys, int* vals) {
-  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || !xy || !depth || !radii || !offsets || !keys || !vals || !a3d_aligned(8, xy)) return A3D_EINVAL;
+  if (!gs_extents_ok(B, N, H, W) || !xy || !depth || !radii || !offsets || !keys || !vals || !a3d_aligned(8, xy, offsets, keys) ||
+      !a3d_aligned(4, depth, radii, vals))
+    return A3D_EINVAL;
   gs_duplicate_kernel<<<blocks_for((int64_t)B * N), 256, 0, (hipStream_t)stream>>>(B, N, H, W, reinterpret_cast<const float2*>(xy), depth, radii,
                                                                                     offsets, reinterpret_cast<uint64_t*>(keys), vals);
   return a3d_launch_status();
 }
 
 extern "C" int a3d_gs_tile_ranges_f32(a3d_stream_t stream, const int64_t* keys, int64_t L, int* ranges, int64_t n_tiles) {
-  if (!ranges || n_tiles <= 0 || L < 0 || L > 0x7fffffffLL || (L > 0 && !keys) || !a3d_aligned(8, ranges)) return A3D_EINVAL;
+  if (!ranges || n_tiles <= 0 || L < 0 || L > 0x7fffffffLL || (L > 0 && !keys) || !a3d_aligned(8, ranges, keys)) return A3D_EINVAL;
   if (hipError_t e = hipMemsetAsync(ranges, 0, n_tiles * 2 * sizeof(int), (hipStream_t)stream); e != hipSuccess) return (int)e;
   if (L == 0) return A3D_OK;
   gs_tile_ranges_kernel<<<blocks_for(L), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const uint64_t*>(keys), L, reinterpret_cast<int2*>(ranges));
@@ -666,8 +673,9 @@ extern "C" int a3d_gs_tile_ranges_f32(a3d_stream_t stream, const int64_t* keys, 
 extern "C" int a3d_gs_render_f32(a3d_stream_t stream, int B, int N, int H, int W, const int* ranges, const int64_t* perm, const int* vals,
                                  const float* xy, const float* conic_o, const float* rgb, const float* depth, const float* bg,
                                  float* out_img, float* out_depth, float* out_alpha, float* T_final, int* n_contrib) {
-  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || !ranges || !xy || !conic_o || !rgb || !depth || !bg || !out_img || !out_depth || !out_alpha ||
-      !T_final || !n_contrib || !a3d_aligned(16, conic_o) || !a3d_aligned(8, xy, ranges))
+  if (!gs_extents_ok(B, N, H, W) || !ranges || !perm || !vals || !xy || !conic_o || !rgb || !depth || !bg || !out_img || !out_depth ||
+      !out_alpha || !T_final || !n_contrib || !a3d_aligned(16, conic_o) || !a3d_aligned(8, xy, ranges, perm) ||
+      !a3d_aligned(4, vals, rgb, depth, bg, out_img, out_depth, out_alpha, T_final, n_contrib))
     return A3D_EINVAL;
   const dim3 grid((W + GS_TILE - 1) / GS_TILE, (H + GS_TILE - 1) / GS_TILE, B);
   gs_render_kernel<<<grid, GS_BLOCK, 0, (hipStream_t)stream>>>(B, N, H, W, reinterpret_cast<const int2*>(ranges), perm, vals,
@@ -680,8 +688,9 @@ extern "C" int a3d_gs_render_bwd_f32(a3d_stream_t stream, int B, int N, int H, i
                                      const float* xy, const float* conic_o, const float* rgb, const float* depth, const float* bg,
                                      const float* T_final, const int* n_contrib, const float* d_img, const float* d_depth,
                                      const float* d_alpha, float* rows) {
-  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || !ranges || !xy || !conic_o || !rgb || !depth || !bg || !T_final || !n_contrib || !d_img ||
-      !a3d_aligned(16, conic_o, rows) || !a3d_aligned(8, xy, ranges))
+  if (!gs_extents_ok(B, N, H, W) || !ranges || !perm || !vals || !xy || !conic_o || !rgb || !depth || !bg || !T_final || !n_contrib ||
+      !d_img || !rows || !a3d_aligned(16, conic_o, rows) || !a3d_aligned(8, xy, ranges, perm) ||
+      !a3d_aligned(4, vals, rgb, depth, bg, T_final, n_contrib, d_img, d_depth, d_alpha))
     return A3D_EINVAL;
   const dim3 grid((W + GS_TILE - 1) / GS_TILE, (H + GS_TILE - 1) / GS_TILE, B);
   gs_render_bwd_kernel<<<grid, GS_BLOCK, 0, (hipStream_t)stream>>>(B, N, H, W, reinterpret_cast<const int2*>(ranges), perm, vals,
@@ -695,7 +704,8 @@ extern "C" int a3d_gs_preprocess_bwd_f32(a3d_stream_t stream, A3D_GS_INPUT_PARAM
                                          float* d_rots, float* d_opac, float* d_shs, float* d_colors) {
   const GsInputs in = make_inputs(A3D_GS_INPUT_ARGS);
   if (!gs_inputs_ok(in) || !radii || !clamped || !offsets || !tiles_touched || !d_means2d || !d_means || !d_scales || !d_rots || !d_opac ||
-      !rows || (shs && !d_shs) || (colors && !d_colors) || !a3d_aligned(16, rows))
+      !rows || (shs && !d_shs) || (colors && !d_colors) || !a3d_aligned(16, rows) || !a3d_aligned(8, offsets) ||
+      !a3d_aligned(4, radii, clamped, tiles_touched, d_means2d, d_means, d_scales, d_rots, d_opac, d_shs, d_colors))
     return A3D_EINVAL;
   gs_preprocess_bwd_kernel<<<blocks_for((int64_t)B * N), 256, 0, (hipStream_t)stream>>>(in, radii, clamped, offsets, tiles_touched, rows, d_means2d,
                                                                                          d_means, d_scales, d_rots, d_opac, d_shs, d_colors);
@@ -703,7 +713,7 @@ extern "C" int a3d_gs_preprocess_bwd_f32(a3d_stream_t stream, A3D_GS_INPUT_PARAM
 }
 
 extern "C" int a3d_gs_sum_batch_f32(a3d_stream_t stream, const float* src, float* dst, int B, int64_t M) {
-  if (!src || !dst || B <= 0 || M <= 0) return A3D_EINVAL;
+  if (!src || !dst || B <= 0 || M <= 0 || !a3d_aligned(4, src, dst)) return A3D_EINVAL;
   sum_leading((hipStream_t)stream, src, dst, B, M);
   return a3d_launch_status();
 }

@@ -399,7 +399,13 @@ int a3d_adamw_f32(a3d_stream_t stream, float* p, const float* g, float* m, float
  *   a3d_gs_render_bwd_f32      d_depth / d_alpha may be NULL (zero); rows [L, 12]: per instance, in duplicated order, the gradient w.r.t.
  *                              centre (2), conic (3), opacity, colour (3), depth, summed over the tile's pixels
  *   a3d_gs_preprocess_bwd_f32  per (image, Gaussian) input gradients [B, N, ...] (d_means2d: NDC centre, third component 0)
- *   a3d_gs_sum_batch_f32       dst[k] = sum over b of src[b * M + k], b in order */
+ *   a3d_gs_sum_batch_f32       dst[k] = sum over b of src[b * M + k], b in order
+ * Preconditions, checked before anything is launched (A3D_EINVAL otherwise):
+ *   - every pointer is required except d_depth / d_alpha, the colour source not in use with its gradient (d_shs / d_colors), and
+ *     keys of a3d_gs_tile_ranges_f32 when L == 0; perm, vals and rows are required even when there are no instances (one element);
+ *   - alignment: conic_o and rows 16 bytes; xy, ranges, keys, offsets and perm 8; every other float / int operand 4;
+ *   - B, N, H, W > 0, B N <= 2^31 - 1, B * tiles <= 2^31 - 1 (tiles = ceil(W / 16) ceil(H / 16)); 0 <= deg <= 3 and
+ *     M >= (deg + 1)^2 with shs; 0 <= L <= 2^31 - 1 and n_tiles > 0 for a3d_gs_tile_ranges_f32; B, M > 0 for a3d_gs_sum_batch_f32. */
 int a3d_gs_preprocess_f32(a3d_stream_t stream, int B, int N, const float* means, int64_t means_bs, const float* scales, int64_t scales_bs,
                           const float* rots, int64_t rots_bs, const float* opac, int64_t opac_bs, const float* shs, int64_t shs_bs, int M,
                           int deg, const float* colors, int64_t colors_bs, const float* view, const float* proj, const float* campos,

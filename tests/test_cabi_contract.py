@@ -3,7 +3,8 @@ the widest access the kernels make through it, or an attention-backward do_scale
 A3D_EINVAL before anything reaches the GPU.  The device addresses below are made up and never dereferenced: every call differs from a
 valid launch in exactly one operand, and the argument checks run before the first HIP call, so this runs on a machine without a GPU.
 (No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)  The forward attention entry
-points, the deformation field's (a3d_dg_*) and the ARAP loss's (a3d_knn_f32, a3d_arap_*) are held to the same discipline further down."""
+points, the deformation field's (a3d_dg_*), the ARAP loss's (a3d_knn_f32, a3d_arap_*) and the splat rasterizer's (a3d_gs_*) are held to
+the same discipline further down."""
 import ctypes
 import math
 
@@ -408,3 +409,108 @@ def test_arap_refuses_bad_geometry(lib, entry):
     bad += [dict(bs=-1), dict(F=65535), dict(F=16385, S=16384), dict(F=1, S=2 ** 28, K=4)]
     for g in bad:
         assert _arap_call(lib, entry, **g) == A3D_EINVAL, f"{entry}: {g}"
+
+
+# ---- splat rasterizer (a3d_gs_*_f32, csrc/splat.hip): fp32 only, one build
+GS_VALID = dict(B=2, N=300, H=40, W=56, M=16, deg=3, L=1000, n_tiles=24, sumB=2, sumM=900)
+GS_INPUTS = ("means", "scales", "rots", "opac", "shs", "colors", "view", "proj", "campos", "tanfovx", "tanfovy")
+GS_OPERANDS = {
+    "a3d_gs_preprocess_f32": GS_INPUTS + ("radii", "xy", "depth", "conic_o", "rgb", "clamped", "tiles_touched"),
+    "a3d_gs_duplicate_f32": ("xy", "depth", "radii", "offsets", "keys", "vals"),
+    "a3d_gs_tile_ranges_f32": ("keys", "ranges"),
+    "a3d_gs_render_f32": ("ranges", "perm", "vals", "xy", "conic_o", "rgb", "depth", "bg", "out_img", "out_depth", "out_alpha", "T_final",
+                          "n_contrib"),
+    "a3d_gs_render_bwd_f32": ("ranges", "perm", "vals", "xy", "conic_o", "rgb", "depth", "bg", "T_final", "n_contrib", "d_img", "d_depth",
+                              "d_alpha", "rows"),
+    "a3d_gs_preprocess_bwd_f32": GS_INPUTS + ("radii", "clamped", "offsets", "tiles_touched", "rows", "d_means2d", "d_means", "d_scales",
+                                              "d_rots", "d_opac", "d_shs", "d_colors"),
+    "a3d_gs_sum_batch_f32": ("src", "dst"),
+}
+GS_ALIGN = dict(conic_o=16, rows=16, xy=8, ranges=8, keys=8, offsets=8, perm=8)          # every other operand: 4 bytes
+GS_ABSENT = ("colors", "d_colors")                      # the valid call renders from shs: the other colour source and its gradient are NULL
+GS_OPTIONAL = ("d_depth", "d_alpha")                    # NULL reads as a zero cotangent: with every other operand valid such a call would launch
+
+
+def _gs_call(lib, entry, ptr=None, **geometry):
+    """The valid launch of `entry` (B = 2, N = 300, 40 x 56, degree-3 SH with M = 16, L = 1000 instances) with the named pointers /
+    geometry words replaced.  Callers replace exactly one, and never none."""
+    assert ptr or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(GS_OPERANDS[entry])
+    p.update({n: None for n in GS_ABSENT if n in p})
+    p.update(ptr or {})
+    g = dict(GS_VALID, **geometry)
+    inputs = [g["B"], g["N"], p.get("means"), 0, p.get("scales"), 0, p.get("rots"), 0, p.get("opac"), 0, p.get("shs"), 0, g["M"],
+              g["deg"], p.get("colors"), 0, p.get("view"), p.get("proj"), p.get("campos"), p.get("tanfovx"), p.get("tanfovy"), g["H"],
+              g["W"], 1.0]
+    dims = [g["B"], g["N"], g["H"], g["W"]]
+    tail = lambda names: [p[n] for n in names]
+    if entry in ("a3d_gs_preprocess_f32", "a3d_gs_preprocess_bwd_f32"):
+        args = [None, *inputs, *tail(GS_OPERANDS[entry][len(GS_INPUTS):])]
+    elif entry == "a3d_gs_tile_ranges_f32":
+        args = [None, p["keys"], g["L"], p["ranges"], g["n_tiles"]]
+    elif entry == "a3d_gs_sum_batch_f32":
+        args = [None, p["src"], p["dst"], g["sumB"], g["sumM"]]
+    else:
+        args = [None, *dims, *tail(GS_OPERANDS[entry])]
+    return getattr(lib, entry)(*args)
+
+
+GS = pytest.mark.parametrize("entry", sorted(GS_OPERANDS))
+GS_WITH_EXTENTS = sorted(set(GS_OPERANDS) - {"a3d_gs_tile_ranges_f32", "a3d_gs_sum_batch_f32"})
+GS_WITH_INPUTS = ("a3d_gs_preprocess_f32", "a3d_gs_preprocess_bwd_f32")
+
+
+@GS
+def test_splat_refuses_misaligned_or_missing_operand(lib, entry):
+    """Every required operand NULL (perm, vals and rows included: they are one element long when nothing is visible, never absent);
+    conic_o and rows 8 bytes off their 16, xy / ranges / keys / offsets / perm 4 bytes off their 8, every other operand 2 bytes off.
+    d_depth / d_alpha may be NULL, so only their misalignment is refused here."""
+    base = _ptrs(GS_OPERANDS[entry])
+    for operand in GS_OPERANDS[entry]:
+        if operand in GS_ABSENT:
+            continue
+        off = GS_ALIGN.get(operand, 4) // 2
+        rc = _gs_call(lib, entry, ptr={operand: base[operand] + off})
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +{off} bytes returned {rc}"
+        if operand not in GS_OPTIONAL:
+            rc = _gs_call(lib, entry, ptr={operand: None})
+            assert rc == A3D_EINVAL, f"{entry}: NULL {operand} returned {rc}"
+    if entry == "a3d_gs_render_bwd_f32":                 # absent cotangents do not rescue a call that is refused for another reason
+        assert _gs_call(lib, entry, ptr=dict(d_depth=None, d_alpha=None, rows=None)) == A3D_EINVAL
+        assert _gs_call(lib, entry, ptr=dict(d_depth=None, d_alpha=None, perm=base["perm"] + 4)) == A3D_EINVAL
+
+
+@pytest.mark.parametrize("entry", GS_WITH_INPUTS)
+def test_splat_refuses_bad_colour_source_and_sh_arguments(lib, entry):
+    """shs and colors both set or both NULL; a colour source without its gradient buffer; deg outside 0 .. 3; M < (deg + 1)^2; a colour
+    source (and its gradient) moved off its 4-byte alignment in the colors form too."""
+    base = _ptrs(GS_OPERANDS[entry])
+    assert _gs_call(lib, entry, ptr=dict(colors=base["colors"])) == A3D_EINVAL, "shs and colors"
+    assert _gs_call(lib, entry, ptr=dict(shs=None)) == A3D_EINVAL, "neither shs nor colors"
+    assert _gs_call(lib, entry, ptr=dict(shs=None, colors=base["colors"] + 2, **({"d_colors": base["d_colors"]} if "d_colors" in base else {}))) \
+        == A3D_EINVAL, "colors at +2 bytes"
+    if "d_colors" in base:
+        assert _gs_call(lib, entry, ptr=dict(shs=None, colors=base["colors"])) == A3D_EINVAL, "colors without d_colors"
+        assert _gs_call(lib, entry, ptr=dict(shs=None, colors=base["colors"], d_colors=base["d_colors"] + 2)) == A3D_EINVAL
+    for g in (dict(deg=-1), dict(deg=4), dict(deg=3, M=15), dict(deg=2, M=8), dict(deg=1, M=3), dict(deg=0, M=0)):
+        assert _gs_call(lib, entry, **g) == A3D_EINVAL, f"{entry}: {g}"
+
+
+@pytest.mark.parametrize("entry", GS_WITH_EXTENTS)
+def test_splat_refuses_bad_extents(lib, entry):
+    """B, N, H, W <= 0; more than 2^31 - 1 (image, Gaussian) pairs; more than 2^31 - 1 (image, tile) ranges."""
+    bad = [{k: v} for k in ("B", "N", "H", "W") for v in (0, -1)]
+    bad += [dict(B=2, N=2 ** 30), dict(B=3, N=2 ** 30), dict(B=2, H=2 ** 19, W=2 ** 19), dict(B=1, H=2 ** 31 - 1, W=2 ** 31 - 1)]
+    for g in bad:
+        assert _gs_call(lib, entry, **g) == A3D_EINVAL, f"{entry}: {g}"
+
+
+def test_splat_tile_ranges_and_sum_batch_refusals(lib):
+    """a3d_gs_tile_ranges_f32: L < 0, L > 2^31 - 1, keys NULL with L > 0, n_tiles <= 0.  a3d_gs_sum_batch_f32: non-positive sizes (its
+    NULL and misaligned pointers are with the other entry points')."""
+    for g in (dict(L=-1), dict(L=2 ** 31), dict(n_tiles=0), dict(n_tiles=-1)):
+        assert _gs_call(lib, "a3d_gs_tile_ranges_f32", **g) == A3D_EINVAL, g
+    assert _gs_call(lib, "a3d_gs_tile_ranges_f32", ptr=dict(keys=None), L=1) == A3D_EINVAL
+    assert _gs_call(lib, "a3d_gs_tile_ranges_f32", ptr=dict(ranges=None), L=0) == A3D_EINVAL
+    for g in (dict(sumB=0), dict(sumB=-1), dict(sumM=0), dict(sumM=-1)):
+        assert _gs_call(lib, "a3d_gs_sum_batch_f32", **g) == A3D_EINVAL, g

@@ -1,6 +1,7 @@
 """CPU checks of the splat rasterizer's host side: the batched camera helpers against the reference's own (tests/golden/gs_camera.npz),
 closed-form checks of the dense restatement tests/gs_ref.py (the GPU tests' oracle), the sort-key packing and the tile rectangle, and
-the render loops of csrc/splat.hip free of scratch."""
+the render loops of csrc/splat.hip free of scratch; and, for the constructed scenes of tests/splat_scenes.py, the decision margins, the
+branch predicates, fp32 / float64 agreement of every decision and the oracle's derivative against finite differences."""
 import math
 import os
 
@@ -138,3 +139,118 @@ def test_render_loops_do_not_touch_scratch(tmp_path):
     for n in found:
         scratch = [t for _, t, _ in kernels[n]["ins"] if t.startswith("scratch_") or "buffer_store_dword" in t and "off, s[0:3]" in t]
         assert not scratch, (n, scratch[:3])
+
+
+# ---- the constructed scenes of tests/splat_scenes.py: what the GPU parity tests (tests/test_splat_edges_gpu.py) rely on, proved on the CPU
+from tests import splat_scenes  # noqa: E402
+
+ALL_SCENES = sorted(splat_scenes.SCENES)
+_ORACLE = {}
+
+
+def _oracle(name, dtype=torch.float64):
+    if (name, dtype) not in _ORACLE:
+        _ORACLE[name, dtype] = splat_scenes.oracle(splat_scenes.SCENES[name], dtype=dtype)
+    return _ORACLE[name, dtype]
+
+
+def test_scene_table_rules():
+    """At most 8 Gaussians outside the seam scenes, at most 700 and 40 x 56 anywhere, non-square tanfov in at least half of the scenes,
+    anisotropic scales, rotations off every axis, centres off the pixel grid."""
+    sc = splat_scenes.SCENES
+    assert all(sc[n]["inputs"]["means3D"].shape[-2] <= (700 if n.startswith("seam_") else 8) for n in sc)
+    assert all(sc[n]["H"] <= 40 and sc[n]["W"] <= 56 for n in sc)
+    assert sum(bool((s["cam"]["tanfovx"] != s["cam"]["tanfovy"]).all()) for s in sc.values()) * 2 >= len(sc)
+    for n, s in sc.items():
+        scales, q = s["inputs"]["scales"].reshape(-1, 3), s["inputs"]["rotations"].reshape(-1, 4)
+        assert bool((scales.max(1).values / scales.min(1).values > 1.02).float().mean() > 0.9), n
+        assert bool(((q / q.norm(dim=1, keepdim=True)).abs().max(1).values < 0.999).float().mean() > 0.99), n
+        xy = _oracle(n)[0]["xy"]                                  # the seam scenes scatter hundreds of centres at random
+        assert n.startswith("seam_") or float((xy - xy.round()).abs().min()) > 1e-3, n
+
+
+@pytest.mark.parametrize("name", ALL_SCENES)
+def test_scene_keeps_its_margins_and_takes_its_branch(name):
+    """Every decision of the contract is at least gs_ref.MIN_MARGINS away from its threshold in float64, the conics are well conditioned,
+    and the branch the scene is for is taken."""
+    sc = splat_scenes.SCENES[name]
+    pre, ex = _oracle(name)
+    m = gs_ref.decision_margins(pre, sc["H"], sc["W"])
+    for k, least in gs_ref.MIN_MARGINS.items():
+        assert m[k] >= least, (name, k, m[k], least)
+    assert m["conic_condition"] <= gs_ref.MAX_CONIC_CONDITION, (name, m["conic_condition"])
+    assert sc["active"](pre, ex), (name, sc["branch"])
+
+
+@pytest.mark.parametrize("name", sorted(splat_scenes.ordinary_counterparts()))
+def test_scene_predicate_fails_on_the_ordinary_counterpart(name):
+    """Centre moved on-screen, opacity 0.5, SH coefficients positive, depths apart: the predicate that proves the branch sees it idle."""
+    sc = splat_scenes.ordinary_counterparts()[name]
+    pre, ex = splat_scenes.oracle(sc)
+    assert not sc["active"](pre, ex), name
+
+
+@pytest.mark.parametrize("name", ALL_SCENES)
+def test_scene_decisions_agree_between_fp32_and_float64(name):
+    """The oracle evaluated in fp32 takes every decision the way float64 does: radii, rectangles, visibility and the per-(pixel,
+    Gaussian) blend mask are identical.  This is what the margins are for, and what makes the fp32 oracle's error a fair yardstick."""
+    (pre64, ex64), (pre32, ex32) = _oracle(name), _oracle(name, torch.float32)
+    assert torch.equal(pre64["radii"], pre32["radii"]), name
+    assert torch.equal(pre64["rect"][pre64["visible"]], pre32["rect"][pre32["visible"]]) and torch.equal(pre64["visible"], pre32["visible"]), name
+    assert torch.equal(ex64["use"], ex32["use"]), (name, int((ex64["use"] != ex32["use"]).sum()))
+    assert torch.equal(ex64["counts"], ex32["counts"]), name
+
+
+def _scene_loss(sc, kw, rest, cot):
+    img, _, dep, alp = gs_ref.rasterize(**kw, **rest)
+    return (img * cot[0]).sum() + (dep * cot[1]).sum() + (alp * cot[2]).sum()
+
+
+@pytest.mark.parametrize("name", ["ewa_clamp_x", "ewa_clamp_y", "ewa_clamp_xy", "alpha_clamp", "sh_clamp", "depth_tie"])
+def test_oracle_gradient_matches_finite_differences(name):
+    """The float64 oracle's autograd is the exact derivative of the contract at the clamps: along two seeded random directions per input
+    (means2D included) it agrees with a central difference of step 1e-6 within 1e-6 relative.  (depth_tie: the two Gaussians of a
+    tied pair move together, since the blending order is not differentiable in their depth difference.)"""
+    sc = splat_scenes.SCENES[name]
+    kw, rest = splat_scenes.to(sc, "cpu", torch.float64, means2D="per_image")
+    B = rest["viewmatrix"].shape[0]
+    g = torch.Generator().manual_seed(7)
+    cot = (torch.randn(B, 3, sc["H"], sc["W"], generator=g, dtype=torch.float64), torch.randn(B, 1, sc["H"], sc["W"], generator=g, dtype=torch.float64) * 0.1,
+           torch.randn(B, 1, sc["H"], sc["W"], generator=g, dtype=torch.float64))
+    grads = dict(zip(kw, torch.autograd.grad(_scene_loss(sc, kw, rest, cot), list(kw.values()))))
+    h = 1e-6
+    with torch.no_grad():
+        for k in kw:
+            for _ in range(2):
+                d = torch.randn(kw[k].shape, generator=g, dtype=torch.float64)
+                if k == "means2D":
+                    d[..., 2] = 0.0
+                if k == "means3D" and name == "depth_tie":
+                    d[:, 1], d[:, 3] = d[:, 0], d[:, 2]
+                plus, minus = dict(kw, **{k: kw[k] + h * d}), dict(kw, **{k: kw[k] - h * d})
+                fd = float(_scene_loss(sc, plus, rest, cot) - _scene_loss(sc, minus, rest, cot)) / (2 * h)
+                an = float((grads[k] * d).sum())
+                assert abs(fd - an) <= 1e-6 * abs(an), (name, k, fd, an)
+
+
+def test_oracle_means2d_gradient_closed_form():
+    """One isotropic Gaussian on the optical axis, loss = sum over pixels of x_pixel * alpha: d loss / d p_proj.x = (W / 2) sum x_pixel
+    alpha (x_pixel - c_x) / var over the blended pixels (alpha >= 1/255; the radius covers every tile), and the third component is 0."""
+    z, s, o = 5.0, 1.0, 0.7
+    t = lambda v: torch.tensor(v, dtype=torch.float64)
+    m2 = torch.zeros(1, 3, dtype=torch.float64, requires_grad=True)
+    img, radii, dep, alp = gs_ref.rasterize(t([[0.0, 0.0, z]]), t([[s, s, s]]), t([[1.0, 0.0, 0.0, 0.0]]), t([[o]]), colors_precomp=t([[0.2, 0.4, 0.6]]),
+                                            bg=t([0.0, 0.0, 0.0]), means2D=m2, **_cam())
+    xs = torch.arange(W, dtype=torch.float64)
+    (alp[0, 0] * xs[None, :]).sum().backward()
+    var = (W / (2 * 0.5) * s / z) ** 2 + 0.3
+    assert int(radii[0, 0]) >= 17
+    want_x = want_y = 0.0
+    for py in range(H):
+        for px in range(W):
+            a = o * math.exp(-0.5 * ((px - 16) ** 2 + (py - 16) ** 2) / var)
+            if a >= 1 / 255:
+                want_x += px * a * (px - 16) / var * W / 2
+                want_y += px * a * (py - 16) / var * H / 2
+    assert abs(want_x) > 1.0 and abs(float(m2.grad[0, 0]) - want_x) <= 1e-10 * abs(want_x)
+    assert abs(float(m2.grad[0, 1]) - want_y) <= 1e-10 * abs(want_x) and float(m2.grad[0, 2]) == 0.0
