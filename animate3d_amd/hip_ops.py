@@ -139,6 +139,11 @@ _SIGNATURES = {
     # reconstruction loss of the 4-D stage (csrc/recon_loss.hip): fp32 only, no storage twins
     "a3d_recon_loss_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_recon_loss_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    # regularisers of the 4-D stage's step (csrc/stage_reg.hip): fp32 only, no storage twins
+    "a3d_image_reg_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
+    "a3d_image_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gaussian_reg_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
+    "a3d_gaussian_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins
     "a3d_clip_preprocess_lds_limit": (c_i64, []),
     "a3d_clip_preprocess": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,

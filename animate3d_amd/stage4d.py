@@ -1,5 +1,5 @@
-"""One optimisation step of the 4-D stage: the reconstruction branch on the gfx950 kernel of csrc/recon_loss.hip, the renderer's policy and
-the step around them.
+"""One optimisation step of the 4-D stage: the reconstruction branch on the gfx950 kernel of csrc/recon_loss.hip, the image and Gaussian
+regularisers on those of csrc/stage_reg.hip, the renderer's policy and the step around them.
 
 The reference's step is ``Animate3DSystem.training_step`` (custom/threestudio-animate3d/systems/animate3d.py:120-370) over
 ``Gaussian4DBatchRenderer.batch_forward`` (renderer/gaussian_batch_renderer_4d.py) and ``DiffGaussian4D.forward``
@@ -24,6 +24,25 @@ is no torch fallback.
   clamp rule), ``d_alpha = g (2 lambda_mask / n_mask)(alpha - m)``, in the planar layout the rasterizer's backward reads.  The upstream
   gradient is read on the device: neither direction synchronises with the host.  Without a gradient to compute nothing is saved.
 
+``image_regularizers(image, depth, alpha, *, lambda_tv, lambda_depth_tv, lambda_sparsity) -> (loss, tv, depth_tv, sparsity)`` and
+``gaussian_regularizers(means, scales, scaling, opacity, *, lambda_position, lambda_scales, lambda_opacity) -> (loss, position, scale_sum,
+opacity_term)``: the six terms of animate3d.py:256-296, one forward and one backward kernel per call.
+
+* ``tv(x) = 2 (sum (x[y+1] - x[y])^2 / (C (H-1) W) + sum (x[x+1] - x[x])^2 / (C H (W-1))) / B`` (threestudio/utils/loss.py:8-16) of
+  ``x = clamp(image, 0, 1)`` (``C = 3``: the ``comp_rgb`` of the reference, never materialised) and, as ``depth_tv``, of the unnormalised
+  ``depth [B, 1, H, W]`` (``C = 1``, no clamp); ``sparsity = mean(sqrt(alpha^2 + 0.01))`` over ``B H W``.  ``H < 2`` or ``W < 2`` with a
+  TV weight raises ``ValueError`` before any launch (the reference divides by zero).  The gradient reaches the raw ``image`` through
+  torch's clamp rule (it passes where ``0 <= image <= 1``, exactly 0 elsewhere; the differences use the clamped neighbours); the backward
+  is gather form, recomputed from the inputs, in the planar layout the rasterizer's backward reads.
+* ``position = mean over (B, N) of |means|`` (the renderer's *unmasked* means; the gradient at a zero-length mean is 0, as
+  ``torch.norm``'s), ``scale_sum = sum(scales)`` (the activated ``[B, N, 3]`` the rasterizer receives; an ``[N, 3]`` expanded over the
+  images is read in place and counted B times), ``opacity_term = sum_N |exp(scaling)| opacity`` with the static Gaussians' log-``scaling``
+  detached: the gradient goes to ``opacity [N, 1]`` / ``[N]`` only.
+* ``loss`` is the weighted sum and the only differentiable output; the named terms are detached and unweighted.  A term whose weight is 0
+  is neither read nor computed (its operand may be ``None``, its named term is 0, its gradient ``None``).  Same rules as the
+  reconstruction loss: fp32 CUDA tensors of exactly these shapes, no atomics (two calls are bitwise equal), the upstream gradient read
+  on the device, nothing but the inputs saved, and nothing at all without a gradient to compute.
+
 ``sampled_frames`` / ``sampled_image_index`` restate the progressive frame schedule (animate3d.py:134-157); ``render_batch`` is the
 renderer for a whole batch with the policy of advanced_4d.py:130-162; ``training_step`` is the step, with either ARAP branch (the k-NN
 graph or the mesh's connectivity); ``vertex_trajectory`` the deformed means of every frame (``save_gaussian_trajectory``);
@@ -43,8 +62,13 @@ from .hip_ops import _p
 from .splat import get_cam_info_gaussian, rasterize_gaussians
 
 PIXELS_PER_BLOCK = 2048          # RL_PIXELS of csrc/recon_loss.hip: one (rgb, mask) partial per block
-UNSUPPORTED_LAMBDAS = ("lambda_tv_loss", "lambda_depth_tv_loss", "lambda_normal_tv", "lambda_position", "lambda_opacity", "lambda_sparsity",
-                       "lambda_scales")       # zero in every released config: not built
+REG_PIXELS_PER_BLOCK = 8192      # IR_PIXELS of csrc/stage_reg.hip: five partials per block
+REG_PAIRS_PER_BLOCK = 1024       # GR_ITEMS of csrc/stage_reg.hip: three partials per block
+UNSUPPORTED_LAMBDAS = ("lambda_normal_tv",)   # the reference's renderer never produces comp_normal, and its own step fails at :354
+IMAGE_REG_LAMBDAS = ("lambda_tv_loss", "lambda_depth_tv_loss", "lambda_sparsity")
+GAUSSIAN_REG_LAMBDAS = ("lambda_position", "lambda_scales", "lambda_opacity")
+REG_ORDER = (("lambda_position", "loss_position"), ("lambda_opacity", "loss_opacity"), ("lambda_sparsity", "loss_sparsity"),
+             ("lambda_scales", "loss_scales"), ("lambda_tv_loss", "loss_tv"), ("lambda_depth_tv_loss", "loss_depth_tv"))   # animate3d.py:256-296
 
 
 # ---- the loss kernel
@@ -126,6 +150,149 @@ def masked_recon_loss(image: torch.Tensor, alpha: torch.Tensor, gt_rgb: torch.Te
     mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
     out = _MaskedReconLoss.apply(image, alpha, gt, mask, index, float(bg), float(lambda_rgb), float(lambda_mask))
     return out[0], out[1].detach(), out[2].detach()
+
+
+# ---- the regularisers (animate3d.py:256-296, threestudio/utils/loss.py:8-16; csrc/stage_reg.hip)
+
+class _ImageReg(torch.autograd.Function):
+    """out [4] = (loss, tv, depth_tv, sparsity); an operand whose lambda is 0 is handed to the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, image, depth, alpha, shape, lambdas):
+        B, H, W = shape
+        ops = [t.detach().contiguous() if lam != 0.0 else None for t, lam in zip((image, depth, alpha), lambdas)]
+        dev = next(t for t in ops if t is not None).device
+        n_partials = B * ((H * W + REG_PIXELS_PER_BLOCK - 1) // REG_PIXELS_PER_BLOCK)
+        partials = torch.empty(5, n_partials, dtype=torch.float32, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        launch("a3d_image_reg_f32", dev, B, H, W, *(_p(t) for t in ops), *lambdas, _p(partials), n_partials, _p(out))
+        ctx.need = tuple(t is not None and need for t, need in zip(ops, ctx.needs_input_grad[:3]))
+        if any(ctx.need):
+            ctx.save_for_backward(*(t if need else None for t, need in zip(ops, ctx.need)))
+            l_tv, l_dtv, l_sp = lambdas
+            down, right, n = (H - 1.0) * W * B, H * (W - 1.0) * B, 1.0 * B * H * W
+            ctx.consts = (shape, (4.0 * l_tv / (3.0 * down) if l_tv else 0.0, 4.0 * l_tv / (3.0 * right) if l_tv else 0.0,
+                                  4.0 * l_dtv / down if l_dtv else 0.0, 4.0 * l_dtv / right if l_dtv else 0.0, l_sp / n))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        ops = ctx.saved_tensors
+        (B, H, W), coefs = ctx.consts
+        g = d_out.detach().float().contiguous()                  # g[0]: the gradient of `loss`; read on the device
+        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.need)]
+        launch("a3d_image_reg_bwd_f32", g.device, B, H, W, *(_p(t) for t in ops), *coefs, _p(g), *(_p(t) for t in grads))
+        return (*grads, None, None)
+
+
+def image_regularizers(image: torch.Tensor, depth: Optional[torch.Tensor], alpha: Optional[torch.Tensor], *, lambda_tv: float,
+                       lambda_depth_tv: float, lambda_sparsity: float):
+    """(loss, tv, depth_tv, sparsity) of the raw render ``image [B, 3, H, W]``, ``depth [B, 1, H, W]`` and ``alpha [B, 1, H, W]`` /
+    ``[B, H, W]``; see the module docstring.  ``depth`` / ``alpha`` may be ``None`` where their weight is 0."""
+    lambdas = (float(lambda_tv), float(lambda_depth_tv), float(lambda_sparsity))
+    if not any(lambdas):
+        raise ValueError("image_regularizers: every weight is 0, there is nothing to compute")
+    if not isinstance(image, torch.Tensor):
+        raise TypeError(f"image: expected a tensor, got {type(image)}")
+    if image.dim() != 4 or image.shape[1] != 3 or 0 in image.shape:
+        raise ValueError(f"image: expected a non-empty [B, 3, H, W], got {tuple(image.shape)}")
+    B, _, H, W = image.shape
+    for name, t, lam, shapes in (("depth", depth, lambdas[1], ((B, 1, H, W),)), ("alpha", alpha, lambdas[2], ((B, 1, H, W), (B, H, W)))):
+        if t is None and lam == 0.0:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{name}: expected {' or '.join(map(str, shapes))}, got {tuple(t.shape)}")
+    if (lambdas[0] or lambdas[1]) and (H < 2 or W < 2):
+        raise ValueError(f"a total-variation term needs H >= 2 and W >= 2, got {H} x {W} (the reference divides by zero)")
+    for name, t in (("image", image), ("depth", depth), ("alpha", alpha)):
+        if t is not None:
+            require_f32_cuda(name, t)
+    out = _ImageReg.apply(image, depth, alpha, (B, H, W), lambdas)
+    return out[0], out[1].detach(), out[2].detach(), out[3].detach()
+
+
+class _GaussianReg(torch.autograd.Function):
+    """out [4] = (loss, position, scale_sum, opacity_term); an operand whose lambda is 0 is handed to the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, means, scales, scaling, opacity, shape, lambdas):
+        B, N = shape
+        l_pos, l_sc, l_op = lambdas
+        m = means.detach().contiguous() if l_pos else None
+        sc, scales_bs = None, 0
+        if l_sc:                                                 # one [N, 3] expanded over the images is read in place, B times
+            shared = scales.stride(0) == 0 and scales[0].is_contiguous()
+            sc, scales_bs = (scales[0].detach(), 0) if shared else (scales.detach().contiguous(), 3 * N)
+        sg, op = (scaling.detach().contiguous(), opacity.detach().contiguous()) if l_op else (None, None)
+        dev = next(t for t in (m, sc, sg) if t is not None).device
+        n_partials = (B * N + REG_PAIRS_PER_BLOCK - 1) // REG_PAIRS_PER_BLOCK
+        partials = torch.empty(3, n_partials, dtype=torch.float32, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        launch("a3d_gaussian_reg_f32", dev, B, N, _p(m), _p(sc), scales_bs, _p(sg), _p(op), *lambdas, _p(partials), n_partials, _p(out))
+        need = ctx.needs_input_grad
+        ctx.need = (bool(l_pos) and need[0], bool(l_sc) and need[1], bool(l_op) and need[3])
+        if any(ctx.need):
+            ctx.save_for_backward(m if ctx.need[0] else None, sg if ctx.need[2] else None)
+            ctx.consts = (shape, (l_pos / (1.0 * B * N), l_sc, l_op), opacity.shape if l_op else None, dev)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        m, sg = ctx.saved_tensors
+        (B, N), coefs, opacity_shape, dev = ctx.consts
+        g = d_out.detach().float().contiguous()
+        d_means = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if ctx.need[0] else None
+        d_scales = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if ctx.need[1] else None
+        d_opacity = torch.empty(opacity_shape, dtype=torch.float32, device=dev) if ctx.need[2] else None
+        launch("a3d_gaussian_reg_bwd_f32", dev, B, N, _p(m), _p(sg), *coefs, _p(g), _p(d_means), _p(d_scales), _p(d_opacity))
+        return d_means, d_scales, None, d_opacity, None, None
+
+
+def gaussian_regularizers(means: Optional[torch.Tensor], scales: Optional[torch.Tensor], scaling: Optional[torch.Tensor],
+                          opacity: Optional[torch.Tensor], *, lambda_position: float, lambda_scales: float, lambda_opacity: float):
+    """(loss, position, scale_sum, opacity_term) of the renderer's unmasked ``means [B, N, 3]`` and activated ``scales [B, N, 3]`` (an
+    expanded ``[N, 3]`` is read in place) and the static Gaussians' log-``scaling [N, 3]`` and ``opacity [N, 1]`` / ``[N]``; see the module
+    docstring.  An operand whose weight is 0 may be ``None``."""
+    lambdas = (float(lambda_position), float(lambda_scales), float(lambda_opacity))
+    if not any(lambdas):
+        raise ValueError("gaussian_regularizers: every weight is 0, there is nothing to compute")
+    given = [("means", means, lambdas[0]), ("scales", scales, lambdas[1]), ("scaling", scaling, lambdas[2]), ("opacity", opacity, lambdas[2])]
+    for name, t, lam in given:
+        if not (isinstance(t, torch.Tensor) or (t is None and lam == 0.0)):
+            raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+    per_image = [t for t in (means, scales) if t is not None]
+    for name, t in (("means", means), ("scales", scales)):
+        if t is not None and (t.dim() != 3 or t.shape[2] != 3 or 0 in t.shape or t.shape != per_image[0].shape):
+            raise ValueError(f"{name}: expected a non-empty [B, N, 3]{' like means' if name == 'scales' else ''}, got {tuple(t.shape)}")
+    B, N = per_image[0].shape[:2] if per_image else (1, scaling.shape[0] if scaling.dim() else 0)
+    if scaling is not None and (tuple(scaling.shape) != (N, 3) or N == 0):
+        raise ValueError(f"scaling: expected a non-empty [{N}, 3], got {tuple(scaling.shape)}")
+    if opacity is not None and tuple(opacity.shape) not in ((N, 1), (N,)):
+        raise ValueError(f"opacity: expected {(N, 1)} or {(N,)}, got {tuple(opacity.shape)}")
+    for name, t, _ in given:
+        if t is not None:
+            require_f32_cuda(name, t)
+    out = _GaussianReg.apply(means, scales, scaling, opacity, (B, N), lambdas)
+    return out[0], out[1].detach(), out[2].detach(), out[3].detach()
+
+
+class _TotalInOrder(torch.autograd.Function):
+    """``total + terms[0] + terms[1] + ...`` added one at a time in fp32, the reference's ``loss += ...``; the gradient goes to ``total``
+    and, unchanged, to the ``carriers``: the differentiable weighted sums of the two regulariser calls, whose terms these are."""
+
+    @staticmethod
+    def forward(ctx, total, n_carriers, *rest):
+        ctx.counts = (n_carriers, len(rest) - n_carriers)
+        value = total.detach()
+        for term in rest[n_carriers:]:
+            value = value + term
+        return value
+
+    @staticmethod
+    def backward(ctx, grad):
+        return (grad, None, *([grad] * ctx.counts[0]), *([None] * ctx.counts[1]))
 
 
 # ---- the frame schedule (animate3d.py:134-157)
@@ -249,8 +416,10 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     [., H, W, 1]`` bool, ``c2w``, ``fovy``, ``timestamps``) and, for a guidance step, ``random_camera`` (``c2w``, ``fovy``, ``timestamps``,
     ``height``, ``width``).  ``guidance``: ``comp_rgb [B, H, W, 3] -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound); a step with a
     guidance callable is the reference's ``load_guidance: true``.  ``loss``: the lambdas under the reference's names (``lambda_rgb``,
-    ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num`` and, for the mesh branch, ``arap_K``); a non-zero value for one
-    this module does not build raises ``NotImplementedError``.  ``bg``: the three background values.  ``render`` is ``render_batch``'s
+    ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num``, for the mesh branch ``arap_K``, and the six regulariser weights
+    ``lambda_tv_loss``, ``lambda_depth_tv_loss``, ``lambda_sparsity``, ``lambda_position``, ``lambda_opacity``, ``lambda_scales``); a
+    non-zero ``lambda_normal_tv`` raises ``NotImplementedError`` (the reference's renderer never produces ``comp_normal``), a negative
+    regulariser weight ``ValueError`` (the reference tests ``> 0.0`` and would drop it silently).  ``bg``: the three background values.  ``render`` is ``render_batch``'s
     stand-in for tests.
 
     ``graph`` chooses the branch of animate3d.py:222-239.  An ``ArapGraph`` is the k-NN graph of ``xyz``, fixed for the stage.  A
@@ -263,11 +432,19 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     In the reference's order: the schedule and the ``(view, frame)`` index; one render of the gathered cameras and the masked RGB / mask
     MSE against ``rgb`` / ``mask`` read through the index; with guidance a render of the random cameras and ``lambda_sds * guidance(comp_rgb)``
     (both renders see the same ``do_guidance``, animate3d.py:131, 188); with ``lambda_arap > 0`` the ARAP energy of the *last* render's
-    first ``len(sampled_frames)`` unmasked means (:218).  Returns ``loss`` and, detached and times their lambdas as the reference logs
-    them, ``loss_rgb``, ``loss_mask``, ``loss_sds``, ``loss_arap`` (the last two only when they are part of the step)."""
+    first ``len(sampled_frames)`` unmasked means (:218); then the regularisers with a non-zero weight, all on the *last* render
+    (:256-296): ``gaussian_regularizers`` and ``image_regularizers`` are each called only when one of their weights is non-zero (a step
+    with all six at 0 launches, draws and returns exactly what it did without them), and their terms are added to the total one by one
+    in the reference's order (position, opacity, sparsity, scales, tv, depth_tv: the fp32 total depends on it).  Returns ``loss`` and,
+    detached and times their lambdas, ``loss_rgb``, ``loss_mask``, ``loss_sds``, ``loss_arap``, ``loss_position``, ``loss_opacity``,
+    ``loss_sparsity``, ``loss_scales``, ``loss_tv``, ``loss_depth_tv`` (all but the first two only when they are part of the step)."""
     for name in UNSUPPORTED_LAMBDAS:
         if float(loss.get(name, 0.0)) != 0.0:
             raise NotImplementedError(f"{name} = {loss[name]}: zero in every released config, not built")
+    reg = {name: float(loss.get(name, 0.0)) for name in IMAGE_REG_LAMBDAS + GAUSSIAN_REG_LAMBDAS}
+    for name, value in reg.items():
+        if value < 0.0:
+            raise ValueError(f"{name} = {value}: the reference tests `> 0.0` and would drop a negative weight without a word")
     do_guidance = guidance is not None
     lambda_arap = float(loss.get("lambda_arap", 0.0))
     if lambda_arap > 0.0 and graph is None:
@@ -280,6 +457,10 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     rgb, mask = batch["rgb"], batch["mask"]
     if rgb.shape[0] != n_view * n_frame:
         raise ValueError(f"batch['rgb']: expected {n_view * n_frame} images (n_view * n_frame), got {rgb.shape[0]}")
+    if reg["lambda_tv_loss"] or reg["lambda_depth_tv_loss"]:      # the last render's size, before anything is rendered
+        h, w = (batch["random_camera"]["height"], batch["random_camera"]["width"]) if do_guidance else rgb.shape[1:3]
+        if h < 2 or w < 2:
+            raise ValueError(f"a total-variation term needs H >= 2 and W >= 2, got {h} x {w} (the reference divides by zero)")
     frames = sampled_frames(global_step, n_frame, progressive_iter_per_frame, do_guidance=do_guidance, strategy=sample_strategy, rng=rng)
     index = sampled_image_index(frames, n_view, n_frame, rgb.device)
     gather = index.long()
@@ -305,6 +486,26 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
                                               sample_num=int(loss.get("arap_sample_num", 512)), generator=generator)
         total = total + loss_arap
         terms["loss_arap"] = loss_arap.detach()
+    if any(reg.values()):                                        # animate3d.py:256-296, all on the last render
+        carriers, unweighted = [], {}
+        if any(reg[name] for name in GAUSSIAN_REG_LAMBDAS):
+            carrier, *named = gaussian_regularizers(out["means3D"] if reg["lambda_position"] else None,
+                                                    out["scales"] if reg["lambda_scales"] else None,
+                                                    gaussians.scaling if reg["lambda_opacity"] else None,
+                                                    gaussians.opacity if reg["lambda_opacity"] else None, lambda_position=reg["lambda_position"],
+                                                    lambda_scales=reg["lambda_scales"], lambda_opacity=reg["lambda_opacity"])
+            carriers.append(carrier)
+            unweighted.update(zip(GAUSSIAN_REG_LAMBDAS, named))
+        if any(reg[name] for name in IMAGE_REG_LAMBDAS):
+            carrier, *named = image_regularizers(out["image"], out["comp_depth"].permute(0, 3, 1, 2) if reg["lambda_depth_tv_loss"] else None,
+                                                 out["alpha"] if reg["lambda_sparsity"] else None, lambda_tv=reg["lambda_tv_loss"],
+                                                 lambda_depth_tv=reg["lambda_depth_tv_loss"], lambda_sparsity=reg["lambda_sparsity"])
+            carriers.append(carrier)
+            unweighted.update(zip(IMAGE_REG_LAMBDAS, named))
+        for name, key in REG_ORDER:                              # the reference's order: the fp32 total depends on it
+            if reg[name]:
+                terms[key] = unweighted[name] * reg[name]
+        total = _TotalInOrder.apply(total, len(carriers), *carriers, *(terms[key] for name, key in REG_ORDER if reg[name]))
     return {"loss": total, **terms}
 
 

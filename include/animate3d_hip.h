@@ -521,6 +521,44 @@ int a3d_recon_loss_bwd_f32(a3d_stream_t stream, int B, int H, int W, const float
                            const uint8_t* gt_mask, const int* index, float bg, float coef_rgb, float coef_mask, const float* grad_out,
                            float* d_image, float* d_alpha);
 
+/* Regularisers of the 4-D stage's step (csrc/stage_reg.hip; contract in animate3d_amd/stage4d.py, image_regularizers and
+ * gaussian_regularizers), fp32.  Replace the torch chains of custom/threestudio-animate3d/systems/animate3d.py:256-296 over tv_loss
+ * (threestudio/utils/loss.py:8-16).  image [B, 3, H, W] planar and unclamped, depth and alpha [B, H, W]; means [B, N, 3]; scales: image b's
+ * [N, 3] at scales + b scales_bs, scales_bs = 3 N or 0 (one [N, 3] counted B times); scaling [N, 3] log-scales; opacity [N].
+ *   a3d_image_reg_f32         out [4] = {lambda_tv tv + lambda_depth_tv depth_tv + lambda_sparsity sparsity, tv, depth_tv, sparsity} with
+ *                             tv = 2 (sum (x[y+1] - x[y])^2 / (3 (H-1) W) + sum (x[x+1] - x[x])^2 / (3 H (W-1))) / B of x = clamp(image, 0, 1),
+ *                             depth_tv the same of depth (one channel, no clamp), sparsity = mean(sqrt(alpha^2 + 0.01)).  A term whose
+ *                             lambda is 0 is neither read nor computed (0 in out) and its pointer may be NULL; all three 0: A3D_EINVAL.
+ *                             partials [5, n_partials] fp32 workspace, n_partials = B * ceil(H W / 8192) (anything else: A3D_EINVAL).
+ *                             No atomics: per-thread runs of 32 pixels, a fixed tree per block, the partials added in index order in fp64
+ *   a3d_image_reg_bwd_f32     gather form, recomputed from the inputs; g = grad_out[0] read on the device.  d_image = g (coef_tv_h (into -
+ *                             out of the pixel vertically) + coef_tv_w (the same horizontally)) of the clamped neighbours where
+ *                             0 <= image <= 1 and exactly 0 elsewhere; d_depth likewise without a clamp; d_alpha = g coef_sparsity alpha /
+ *                             sqrt(alpha^2 + 0.01).  The caller passes coef_tv_h = 4 lambda_tv / (3 (H-1) W B), coef_tv_w = 4 lambda_tv /
+ *                             (3 H (W-1) B), the depth's without the 3, coef_sparsity = lambda_sparsity / (B H W).  Each of d_image / d_depth
+ *                             / d_alpha may be NULL, not all; the input of a NULL output is not read and may be NULL
+ *   a3d_gaussian_reg_f32      out [4] = {lambda_position position + lambda_scales scale_sum + lambda_opacity opacity_term, position,
+ *                             scale_sum, opacity_term}: position = mean over (B, N) of |means|, scale_sum = sum of scales, opacity_term =
+ *                             sum over N of |exp(scaling)| opacity.  Lambdas and NULLs as above.  partials [3, n_partials],
+ *                             n_partials = ceil(B N / 1024)
+ *   a3d_gaussian_reg_bwd_f32  d_means [B, N, 3] = g coef_position means / |means| (0 at |means| = 0), d_scales [B, N, 3] = g coef_scales,
+ *                             d_opacity [N] = g coef_opacity |exp(scaling)|; the caller passes coef_position = lambda_position / (B N) and
+ *                             the other two lambdas.  Each output may be NULL, not all
+ * Pointers are 4-byte aligned at least (A3D_EINVAL otherwise); where W % 4 == 0 and every image pointer is 16-byte aligned the image kernels
+ * read and write 16 bytes at a time.  B, H, W, N > 0, H W <= 2^30, B N <= 2^30, and H, W >= 2 with a TV term (A3D_EINVAL), checked before
+ * the first HIP call. */
+int a3d_image_reg_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* depth, const float* alpha, double lambda_tv,
+                      double lambda_depth_tv, double lambda_sparsity, float* partials, int64_t n_partials, float* out);
+int a3d_image_reg_bwd_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* depth, const float* alpha,
+                          float coef_tv_h, float coef_tv_w, float coef_depth_tv_h, float coef_depth_tv_w, float coef_sparsity,
+                          const float* grad_out, float* d_image, float* d_depth, float* d_alpha);
+int a3d_gaussian_reg_f32(a3d_stream_t stream, int B, int N, const float* means, const float* scales, int64_t scales_bs, const float* scaling,
+                         const float* opacity, double lambda_position, double lambda_scales, double lambda_opacity, float* partials,
+                         int64_t n_partials, float* out);
+int a3d_gaussian_reg_bwd_f32(a3d_stream_t stream, int B, int N, const float* means, const float* scaling, float coef_position,
+                             float coef_scales, float coef_opacity, const float* grad_out, float* d_means, float* d_scales,
+                             float* d_opacity);
+
 /* CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip; contract in animate3d_amd/clip.py, preprocess_frames).
  * Replaces the device -> host -> PIL -> CLIPImageProcessor -> device round trip of animatemv_guidance.py:546-555 / utils/util.py:268-287,
  * bit-equal to it: (uint8)(v * 255.0f), Pillow's 8-bit bicubic resampler (integer, 22 precision bits, horizontal then vertical pass, a
