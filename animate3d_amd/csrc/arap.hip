@@ -11,7 +11,7 @@
 //                        (Hestenes) SVD, which is accurate in the small singular values too; the proper rotation is assembled from the two
 //                        dominant singular pairs, R = w0 u0^T + w1 u1^T + (w0 x w1)(u0 x u1)^T, which equals W U^T where det > 0 and W U^T with
 //                        the smallest singular value's column of U flipped where det <= 0.
-//   arap_reduce_kernel   the F * S energies summed in a fixed order by one block
+//   arap_reduce_kernel   the F * S energies summed in a fixed order by one block: thread t adds t, t + 256, ..., then loss_reduce.h's tree
 //   arap_bwd_kernel      gather form: one thread per (frame, vertex) walks the vertex's entries of the inverse list (sorted (sample, slot)
 //                        pairs: slot 0 the sample's centre, slot k + 1 its k-th neighbour); no atomics, rows without entries are written 0
 //   mesh_sample_kernel   the mesh branch's per-step neighbour draw (sample_matrix_vectorized, util.py:320-344: rand + masked add + sort +
@@ -19,6 +19,7 @@
 //                        sampling (Knuth's Algorithm S) on Philox4x32-10 words keyed by (seed, vertex, position).  Integers only, no LDS,
 //                        no per-thread array, nothing that depends on a maximum degree or on the launch geometry
 #include "f32_common.h"
+#include "loss_reduce.h"
 
 #ifndef A3D_STORAGE_F16
 #include <math.h>
@@ -28,7 +29,6 @@ namespace {
 constexpr int KNN_BLOCK = 256;
 constexpr int KNN_TILE = 1024;        // 16 KiB of LDS per block
 constexpr int ARAP_BLOCK = 128;
-constexpr int ARAP_RED = 256;
 
 template <int K>
 __global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(int N, const float* __restrict__ pts, int Kout, int least, float r2, int* __restrict__ nn_idx,
@@ -266,17 +266,13 @@ __global__ __launch_bounds__(ARAP_BLOCK) void arap_energy_kernel(ArapArgs a, dou
   energy[p] = e;
 }
 
-__global__ __launch_bounds__(ARAP_RED) void arap_reduce_kernel(const double* __restrict__ energy, int n, float* __restrict__ loss) {
-  __shared__ double part[ARAP_RED];
+__global__ __launch_bounds__(LR_BLOCK) void arap_reduce_kernel(const double* __restrict__ energy, int n, float* __restrict__ loss) {
+  __shared__ double part[1][LR_BLOCK];
   double acc = 0.0;
-  for (int i = threadIdx.x; i < n; i += ARAP_RED) acc += energy[i];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = ARAP_RED / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)part[0];
+  for (int i = threadIdx.x; i < n; i += LR_BLOCK) acc += energy[i];
+  part[0][threadIdx.x] = acc;
+  lr_tree(part);
+  if (threadIdx.x == 0) loss[0] = (float)part[0][0];
 }
 
 // adds to acc the derivative of frame f's energy of sample s with respect to the vertex in slot c (0: the centre, k + 1: neighbour k)
@@ -428,7 +424,7 @@ extern "C" int a3d_arap_energy_f32(a3d_stream_t stream, int F, int Nv, int K, in
   hipStream_t st = (hipStream_t)stream;
   const int n = F * S;
   arap_energy_kernel<<<(n + ARAP_BLOCK - 1) / ARAP_BLOCK, ARAP_BLOCK, 0, st>>>(a, rot, rot_f32, energy);
-  arap_reduce_kernel<<<1, ARAP_RED, 0, st>>>(energy, n, loss);
+  arap_reduce_kernel<<<1, LR_BLOCK, 0, st>>>(energy, n, loss);
   return a3d_launch_status();
 }
 

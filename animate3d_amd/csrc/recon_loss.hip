@@ -5,22 +5,21 @@
 //
 //   recon_fwd_kernel<VEC>   block j of image b covers pixels [j RL_PIXELS, (j + 1) RL_PIXELS) of that image; a thread accumulates RL_RUN
 //                           pixels in fp32 (VEC: as RL_RUN / 4 groups of four neighbours, read 16 bytes at a time from the three colour
-//                           planes, the alpha plane and the interleaved ground truth, four mask bytes at once), then a fixed tree over the
-//                           block writes one (rgb, mask) partial.  VEC needs H W % 4 == 0 and 16-byte bases: then every group starts on 16
-//                           bytes in every operand.
-//   recon_final_kernel      one block adds the partials in index order (thread t: t, t + 256, ... in fp64, then a fixed tree): no atomics,
-//                           two calls are bitwise equal.  out = {lambda_rgb mean_rgb + lambda_mask mean_mask, mean_rgb, mean_mask}
+//                           planes, the alpha plane and the interleaved ground truth, four mask bytes at once), then the block writes
+//                           one (rgb, mask) partial.  VEC needs H W % 4 == 0 and 16-byte bases: then every group starts on 16 bytes in
+//                           every operand.
+//   recon_final_kernel      one block adds the partials; the order of both steps is loss_reduce.h's (no atomics, two calls are bitwise
+//                           equal).  out = {lambda_rgb mean_rgb + lambda_mask mean_mask, mean_rgb, mean_mask}
 //   recon_bwd_kernel<VEC>   recomputes from the four inputs in the same geometry and writes d_image / d_alpha in the planar layout
 //                           a3d_gs_render_bwd_f32 reads; the upstream gradient is read through a device pointer
-#include "common.h"
+#include "loss_reduce.h"
 
 #ifndef A3D_STORAGE_F16
 
 namespace {
 
-constexpr int RL_BLOCK = 256;
 constexpr int RL_RUN = 8;                          // pixels per thread
-constexpr int RL_PIXELS = RL_BLOCK * RL_RUN;       // pixels per block: a3d_recon_loss_f32's partials are B * ceil(H W / RL_PIXELS) pairs
+constexpr int RL_PIXELS = LR_BLOCK * RL_RUN;       // pixels per block: a3d_recon_loss_f32's partials are B * ceil(H W / RL_PIXELS) pairs
 static_assert(RL_RUN % 4 == 0 && RL_RUN <= 64, "a thread's run is a bounded number of 4-pixel groups");
 
 struct ReconArgs {
@@ -62,8 +61,8 @@ A3D_DEV ReconBlock rl_block(const ReconArgs& a) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(RL_BLOCK) void recon_fwd_kernel(ReconArgs a, float* __restrict__ partials, int64_t n_partials) {
-  __shared__ float red[2][RL_BLOCK];
+__global__ __launch_bounds__(LR_BLOCK) void recon_fwd_kernel(ReconArgs a, float* __restrict__ partials, int64_t n_partials) {
+  __shared__ float red[2][LR_BLOCK];
   const ReconBlock k = rl_block(a);
   const float* img = a.image + k.b * 3 * a.P;
   const float* alp = a.alpha + k.b * a.P;
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(RL_BLOCK) void recon_fwd_kernel(ReconArgs a, float*
   if (VEC) {
 #pragma unroll
     for (int i = 0; i < RL_RUN / 4; ++i) {
-      const int64_t p = k.p0 + 4 * ((int64_t)i * RL_BLOCK + threadIdx.x);
+      const int64_t p = k.p0 + 4 * ((int64_t)i * LR_BLOCK + threadIdx.x);
       if (p < a.P) {                                 // P % 4 == 0: the whole group is inside
         const float4 r = *reinterpret_cast<const float4*>(img + p), g = *reinterpret_cast<const float4*>(img + a.P + p),
                      bl = *reinterpret_cast<const float4*>(img + 2 * a.P + p), al = *reinterpret_cast<const float4*>(alp + p);
@@ -89,45 +88,18 @@ __global__ __launch_bounds__(RL_BLOCK) void recon_fwd_kernel(ReconArgs a, float*
   } else {
 #pragma unroll
     for (int i = 0; i < RL_RUN; ++i) {
-      const int64_t p = k.p0 + (int64_t)i * RL_BLOCK + threadIdx.x;
+      const int64_t p = k.p0 + (int64_t)i * LR_BLOCK + threadIdx.x;
       if (p < a.P)
         rl_pixel(img[p], img[a.P + p], img[2 * a.P + p], alp[p], gt[3 * p], gt[3 * p + 1], gt[3 * p + 2], msk[p] != 0, a.bg, acc_rgb, acc_mask);
     }
   }
-  red[0][threadIdx.x] = acc_rgb;
-  red[1][threadIdx.x] = acc_mask;
-  __syncthreads();
-  for (int h = RL_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + h];
-      red[1][threadIdx.x] += red[1][threadIdx.x + h];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = red[0][0];
-    partials[n_partials + blockIdx.x] = red[1][0];
-  }
+  lr_block_partials<2>({acc_rgb, acc_mask}, red, partials, n_partials);
 }
 
-__global__ __launch_bounds__(RL_BLOCK) void recon_final_kernel(const float* __restrict__ partials, int64_t n_partials, double n_rgb, double n_mask,
+__global__ __launch_bounds__(LR_BLOCK) void recon_final_kernel(const float* __restrict__ partials, int64_t n_partials, double n_rgb, double n_mask,
                                                                double lambda_rgb, double lambda_mask, float* __restrict__ out) {
-  __shared__ double red[2][RL_BLOCK];
-  double s_rgb = 0.0, s_mask = 0.0;
-  for (int64_t i = threadIdx.x; i < n_partials; i += RL_BLOCK) {
-    s_rgb += (double)partials[i];
-    s_mask += (double)partials[n_partials + i];
-  }
-  red[0][threadIdx.x] = s_rgb;
-  red[1][threadIdx.x] = s_mask;
-  __syncthreads();
-  for (int h = RL_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + h];
-      red[1][threadIdx.x] += red[1][threadIdx.x + h];
-    }
-    __syncthreads();
-  }
+  __shared__ double red[2][LR_BLOCK];
+  lr_final_sums<2>(partials, n_partials, red);
   if (threadIdx.x == 0) {
     const double m_rgb = red[0][0] / n_rgb, m_mask = red[1][0] / n_mask;
     out[0] = (float)(lambda_rgb * m_rgb + lambda_mask * m_mask);
@@ -137,7 +109,7 @@ __global__ __launch_bounds__(RL_BLOCK) void recon_final_kernel(const float* __re
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(RL_BLOCK) void recon_bwd_kernel(ReconArgs a, float coef_rgb, float coef_mask, const float* __restrict__ grad_out,
+__global__ __launch_bounds__(LR_BLOCK) void recon_bwd_kernel(ReconArgs a, float coef_rgb, float coef_mask, const float* __restrict__ grad_out,
                                                              float* __restrict__ d_image, float* __restrict__ d_alpha) {
   const ReconBlock k = rl_block(a);
   const float g = grad_out[0];
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(RL_BLOCK) void recon_bwd_kernel(ReconArgs a, float 
   if (VEC) {
 #pragma unroll
     for (int i = 0; i < RL_RUN / 4; ++i) {
-      const int64_t p = k.p0 + 4 * ((int64_t)i * RL_BLOCK + threadIdx.x);
+      const int64_t p = k.p0 + 4 * ((int64_t)i * LR_BLOCK + threadIdx.x);
       if (p < a.P) {
         const uint32_t m = *reinterpret_cast<const uint32_t*>(msk + p);
         const bool m0 = (m & 0xffu) != 0, m1 = (m & 0xff00u) != 0, m2 = (m & 0xff0000u) != 0, m3 = (m & 0xff000000u) != 0;
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(RL_BLOCK) void recon_bwd_kernel(ReconArgs a, float 
   } else {
 #pragma unroll
     for (int i = 0; i < RL_RUN; ++i) {
-      const int64_t p = k.p0 + (int64_t)i * RL_BLOCK + threadIdx.x;
+      const int64_t p = k.p0 + (int64_t)i * LR_BLOCK + threadIdx.x;
       if (p < a.P) {
         const bool m = msk[p] != 0;
         if (di) {
@@ -218,9 +190,9 @@ extern "C" int a3d_recon_loss_f32(a3d_stream_t stream, int B, int H, int W, cons
   const int64_t blocks = recon_args(a, B, H, W, image, alpha, gt_rgb, gt_mask, index, bg);
   if (blocks == 0 || !partials || !out || !a3d_aligned(4, partials, out) || n_partials != blocks) return A3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (recon_vec(a, nullptr, nullptr)) recon_fwd_kernel<true><<<(unsigned)blocks, RL_BLOCK, 0, st>>>(a, partials, n_partials);
-  else recon_fwd_kernel<false><<<(unsigned)blocks, RL_BLOCK, 0, st>>>(a, partials, n_partials);
-  recon_final_kernel<<<1, RL_BLOCK, 0, st>>>(partials, n_partials, 3.0 * (double)B * (double)a.P, (double)B * (double)a.P, lambda_rgb,
+  if (recon_vec(a, nullptr, nullptr)) recon_fwd_kernel<true><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, partials, n_partials);
+  else recon_fwd_kernel<false><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, partials, n_partials);
+  recon_final_kernel<<<1, LR_BLOCK, 0, st>>>(partials, n_partials, 3.0 * (double)B * (double)a.P, (double)B * (double)a.P, lambda_rgb,
                                              lambda_mask, out);
   return a3d_launch_status();
 }
@@ -232,8 +204,8 @@ extern "C" int a3d_recon_loss_bwd_f32(a3d_stream_t stream, int B, int H, int W, 
   const int64_t blocks = recon_args(a, B, H, W, image, alpha, gt_rgb, gt_mask, index, bg);
   if (blocks == 0 || !grad_out || (!d_image && !d_alpha) || !a3d_aligned(4, grad_out, d_image, d_alpha)) return A3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (recon_vec(a, d_image, d_alpha)) recon_bwd_kernel<true><<<(unsigned)blocks, RL_BLOCK, 0, st>>>(a, coef_rgb, coef_mask, grad_out, d_image, d_alpha);
-  else recon_bwd_kernel<false><<<(unsigned)blocks, RL_BLOCK, 0, st>>>(a, coef_rgb, coef_mask, grad_out, d_image, d_alpha);
+  if (recon_vec(a, d_image, d_alpha)) recon_bwd_kernel<true><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, coef_rgb, coef_mask, grad_out, d_image, d_alpha);
+  else recon_bwd_kernel<false><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, coef_rgb, coef_mask, grad_out, d_image, d_alpha);
   return a3d_launch_status();
 }
 

@@ -8,27 +8,25 @@
 //                             non-zero weight (three colour planes, depth, alpha): a run of whole rows at the stage's widths, so of the
 //                             below-neighbours only the last row's, W of IR_PIXELS, lie in another block's run.  A thread accumulates
 //                             IR_RUN pixels in fp32 as groups of G neighbours (G = 4: 16-byte reads; needs W % 4 == 0, so that a group
-//                             lies in one row and its below-neighbours start on 16 bytes too, and 16-byte bases), then a fixed tree over
-//                             the block writes the five partials (tv down / right, depth-tv down / right, sparsity)
+//                             lies in one row and its below-neighbours start on 16 bytes too, and 16-byte bases), then the block writes
+//                             the five partials (tv down / right, depth-tv down / right, sparsity)
 //   gauss_reg_fwd_kernel      the same over (image, Gaussian) pairs: GR_RUN pairs per thread, three partials
-//   sr_final_kernel           one block adds the partials in index order (thread t: t, t + 256, ... in fp64, then a fixed tree): no
-//                             atomics, two calls are bitwise equal.  out = {sum of lambda * term, term 0, term 1, term 2}
+//   sr_final_kernel<K>        one block adds the K rows of partials; the order of both steps is loss_reduce.h's (no atomics, two calls
+//                             are bitwise equal).  out = {sum of lambda * term, term 0, term 1, term 2}
 //   image_reg_bwd_kernel<G>   gather form in the same geometry: the thread of pixel (y, x) recomputes its up to four differences from
 //                             the inputs and writes d_image / d_depth / d_alpha in the planar layout a3d_gs_render_bwd_f32 reads
 //   gauss_reg_bwd_kernel      d_means = c m / |m| (0 at |m| = 0, as torch.norm's backward), a constant d_scales, d_opacity = c |exp(s)|
 // The upstream gradient is read through a device pointer; nothing but the inputs is needed.
-#include "common.h"
+#include "loss_reduce.h"
 
 #ifndef A3D_STORAGE_F16
 
 namespace {
 
-constexpr int SR_BLOCK = 256;
 constexpr int IR_RUN = 32;                         // pixels per thread
-constexpr int IR_PIXELS = SR_BLOCK * IR_RUN;       // pixels per block: a3d_image_reg_f32's partials are B * ceil(H W / IR_PIXELS) fives
+constexpr int IR_PIXELS = LR_BLOCK * IR_RUN;       // pixels per block: a3d_image_reg_f32's partials are B * ceil(H W / IR_PIXELS) fives
 constexpr int GR_RUN = 4;                          // (image, Gaussian) pairs per thread
-constexpr int GR_ITEMS = SR_BLOCK * GR_RUN;        // pairs per block: a3d_gaussian_reg_f32's partials are ceil(B N / GR_ITEMS) threes
-constexpr int SR_MAX_SUMS = 5;
+constexpr int GR_ITEMS = LR_BLOCK * GR_RUN;        // pairs per block: a3d_gaussian_reg_f32's partials are ceil(B N / GR_ITEMS) threes
 static_assert(IR_RUN % 4 == 0, "a thread's run is a whole number of 4-pixel groups");
 
 template <int G>
@@ -51,50 +49,22 @@ A3D_DEV void sr_store(float* p, const float (&v)[G]) {
 template <bool CLAMP>
 A3D_DEV float sr_val(float v) { return CLAMP ? fminf(fmaxf(v, 0.f), 1.f) : v; }
 
-// a fixed tree over the block; thread 0 writes the K sums to partials[k * n_partials + blockIdx.x]
-template <int K>
-A3D_DEV void sr_block_partials(const float (&acc)[K], float (&red)[K][SR_BLOCK], float* __restrict__ partials, int64_t n_partials) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) red[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int h = SR_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + h];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) partials[k * n_partials + blockIdx.x] = red[k][0];
-  }
-}
-
 // how the K sums become the three terms: sum k is scaled by scale[k] and added to term[k]; out[0] = sum of lambda[t] * term t
+template <int K>
 struct SrFinal {
-  int K;
-  int term[SR_MAX_SUMS];
-  double scale[SR_MAX_SUMS];
+  int term[K];
+  double scale[K];
   double lambda[3];
 };
 
-__global__ __launch_bounds__(SR_BLOCK) void sr_final_kernel(const float* __restrict__ partials, int64_t n_partials, SrFinal f,
+template <int K>
+__global__ __launch_bounds__(LR_BLOCK) void sr_final_kernel(const float* __restrict__ partials, int64_t n_partials, SrFinal<K> f,
                                                             float* __restrict__ out) {
-  __shared__ double red[SR_MAX_SUMS][SR_BLOCK];
-  for (int k = 0; k < f.K; ++k) {
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n_partials; i += SR_BLOCK) s += (double)partials[k * n_partials + i];
-    red[k][threadIdx.x] = s;
-  }
-  __syncthreads();
-  for (int h = SR_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h)
-      for (int k = 0; k < f.K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + h];
-    __syncthreads();
-  }
+  __shared__ double red[K][LR_BLOCK];
+  lr_final_sums<K>(partials, n_partials, red);
   if (threadIdx.x == 0) {
     double t[3] = {0.0, 0.0, 0.0};
-    for (int k = 0; k < f.K; ++k) t[f.term[k]] += f.scale[k] * red[k][0];
+    for (int k = 0; k < K; ++k) t[f.term[k]] += f.scale[k] * red[k][0];
     out[0] = (float)(f.lambda[0] * t[0] + f.lambda[1] * t[1] + f.lambda[2] * t[2]);
     out[1] = (float)t[0];
     out[2] = (float)t[1];
@@ -140,14 +110,14 @@ A3D_DEV void ir_tv_fwd(const float* __restrict__ pl, int p, int x, bool below, i
 }
 
 template <int G>
-__global__ __launch_bounds__(SR_BLOCK) void image_reg_fwd_kernel(ImageRegArgs a, float* __restrict__ partials, int64_t n_partials) {
-  __shared__ float red[5][SR_BLOCK];
+__global__ __launch_bounds__(LR_BLOCK) void image_reg_fwd_kernel(ImageRegArgs a, float* __restrict__ partials, int64_t n_partials) {
+  __shared__ float red[5][LR_BLOCK];
   const int64_t b = (int64_t)blockIdx.x / a.chunks;
   const int p0 = (int)((int64_t)blockIdx.x % a.chunks) * IR_PIXELS;
   float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < IR_RUN / G; ++i) {
-    const int p = p0 + G * (i * SR_BLOCK + (int)threadIdx.x);
+    const int p = p0 + G * (i * LR_BLOCK + (int)threadIdx.x);
     if (p < a.P) {                                     // G = 4: P % 4 == 0, the whole group is inside and in one row
       const int y = p / a.W, x = p - y * a.W;
       const bool below = y + 1 < a.H;
@@ -164,7 +134,7 @@ __global__ __launch_bounds__(SR_BLOCK) void image_reg_fwd_kernel(ImageRegArgs a,
       }
     }
   }
-  sr_block_partials<5>(acc, red, partials, n_partials);
+  lr_block_partials<5>(acc, red, partials, n_partials);
 }
 
 // d tv / d pl of the G pixels at p: ch (into - out of, vertically) + cw (the same horizontally), through the clamp rule for the render
@@ -204,7 +174,7 @@ struct ImageRegCoefs {
 };
 
 template <int G>
-__global__ __launch_bounds__(SR_BLOCK) void image_reg_bwd_kernel(ImageRegArgs a, ImageRegCoefs k, const float* __restrict__ grad_out,
+__global__ __launch_bounds__(LR_BLOCK) void image_reg_bwd_kernel(ImageRegArgs a, ImageRegCoefs k, const float* __restrict__ grad_out,
                                                                  float* __restrict__ d_image, float* __restrict__ d_depth,
                                                                  float* __restrict__ d_alpha) {
   const int64_t b = (int64_t)blockIdx.x / a.chunks;
@@ -212,7 +182,7 @@ __global__ __launch_bounds__(SR_BLOCK) void image_reg_bwd_kernel(ImageRegArgs a,
   const float g = grad_out[0];
 #pragma unroll
   for (int i = 0; i < IR_RUN / G; ++i) {
-    const int p = p0 + G * (i * SR_BLOCK + (int)threadIdx.x);
+    const int p = p0 + G * (i * LR_BLOCK + (int)threadIdx.x);
     if (p < a.P) {
       const int y = p / a.W, x = p - y * a.W;
       if (d_image) {
@@ -264,12 +234,12 @@ A3D_DEV float gr_norm3(float x, float y, float z) { return sqrtf(x * x + y * y +
 
 A3D_DEV float gr_scale_norm(const float* __restrict__ s) { return gr_norm3(expf(s[0]), expf(s[1]), expf(s[2])); }
 
-__global__ __launch_bounds__(SR_BLOCK) void gauss_reg_fwd_kernel(GaussRegArgs a, float* __restrict__ partials, int64_t n_partials) {
-  __shared__ float red[3][SR_BLOCK];
+__global__ __launch_bounds__(LR_BLOCK) void gauss_reg_fwd_kernel(GaussRegArgs a, float* __restrict__ partials, int64_t n_partials) {
+  __shared__ float red[3][LR_BLOCK];
   float acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int r = 0; r < GR_RUN; ++r) {
-    const int i = (int)blockIdx.x * GR_ITEMS + r * SR_BLOCK + (int)threadIdx.x;
+    const int i = (int)blockIdx.x * GR_ITEMS + r * LR_BLOCK + (int)threadIdx.x;
     if (i < a.BN) {
       if (a.means) {
         const float* m = a.means + (int64_t)i * 3;
@@ -285,16 +255,16 @@ __global__ __launch_bounds__(SR_BLOCK) void gauss_reg_fwd_kernel(GaussRegArgs a,
       if (a.scaling && i < a.N) acc[2] += gr_scale_norm(a.scaling + (int64_t)i * 3) * a.opacity[i];
     }
   }
-  sr_block_partials<3>(acc, red, partials, n_partials);
+  lr_block_partials<3>(acc, red, partials, n_partials);
 }
 
-__global__ __launch_bounds__(SR_BLOCK) void gauss_reg_bwd_kernel(GaussRegArgs a, float coef_position, float coef_scales, float coef_opacity,
+__global__ __launch_bounds__(LR_BLOCK) void gauss_reg_bwd_kernel(GaussRegArgs a, float coef_position, float coef_scales, float coef_opacity,
                                                                  const float* __restrict__ grad_out, float* __restrict__ d_means,
                                                                  float* __restrict__ d_scales, float* __restrict__ d_opacity) {
   const float g = grad_out[0];
 #pragma unroll
   for (int r = 0; r < GR_RUN; ++r) {
-    const int i = (int)blockIdx.x * GR_ITEMS + r * SR_BLOCK + (int)threadIdx.x;
+    const int i = (int)blockIdx.x * GR_ITEMS + r * LR_BLOCK + (int)threadIdx.x;
     if (i < a.BN) {
       if (d_means) {
         const float* m = a.means + (int64_t)i * 3;
@@ -334,15 +304,15 @@ extern "C" int a3d_image_reg_f32(a3d_stream_t stream, int B, int H, int W, const
                                         lambda_sparsity != 0.0 ? alpha : nullptr);
   if (blocks == 0 || !partials || !out || !a3d_aligned(4, partials, out) || n_partials != blocks) return A3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (image_reg_vec(a, nullptr, nullptr, nullptr)) image_reg_fwd_kernel<4><<<(unsigned)blocks, SR_BLOCK, 0, st>>>(a, partials, n_partials);
-  else image_reg_fwd_kernel<1><<<(unsigned)blocks, SR_BLOCK, 0, st>>>(a, partials, n_partials);
+  if (image_reg_vec(a, nullptr, nullptr, nullptr)) image_reg_fwd_kernel<4><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, partials, n_partials);
+  else image_reg_fwd_kernel<1><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, partials, n_partials);
   // tv(x) = 2 (sum_down / (C (H - 1) W) + sum_right / (C H (W - 1))) / B (threestudio/utils/loss.py:8-16); sparsity: a mean over B H W
   const double h = H, w = W, tv = 2.0 / (double)B;
   const double down = (h - 1.0) * w, right = h * (w - 1.0);                                 // 0 only where no TV term is on
-  SrFinal f{5, {0, 0, 1, 1, 2}, {a.image ? tv / (3.0 * down) : 0.0, a.image ? tv / (3.0 * right) : 0.0, a.depth ? tv / down : 0.0,
-                                 a.depth ? tv / right : 0.0, 1.0 / ((double)B * h * w)},
-            {lambda_tv, lambda_depth_tv, lambda_sparsity}};
-  sr_final_kernel<<<1, SR_BLOCK, 0, st>>>(partials, n_partials, f, out);
+  SrFinal<5> f{{0, 0, 1, 1, 2}, {a.image ? tv / (3.0 * down) : 0.0, a.image ? tv / (3.0 * right) : 0.0, a.depth ? tv / down : 0.0,
+                                a.depth ? tv / right : 0.0, 1.0 / ((double)B * h * w)},
+               {lambda_tv, lambda_depth_tv, lambda_sparsity}};
+  sr_final_kernel<5><<<1, LR_BLOCK, 0, st>>>(partials, n_partials, f, out);
   return a3d_launch_status();
 }
 
@@ -356,9 +326,9 @@ extern "C" int a3d_image_reg_bwd_f32(a3d_stream_t stream, int B, int H, int W, c
   hipStream_t st = (hipStream_t)stream;
   const ImageRegCoefs k{coef_tv_h, coef_tv_w, coef_depth_tv_h, coef_depth_tv_w, coef_sparsity};
   if (image_reg_vec(a, d_image, d_depth, d_alpha))
-    image_reg_bwd_kernel<4><<<(unsigned)blocks, SR_BLOCK, 0, st>>>(a, k, grad_out, d_image, d_depth, d_alpha);
+    image_reg_bwd_kernel<4><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, k, grad_out, d_image, d_depth, d_alpha);
   else
-    image_reg_bwd_kernel<1><<<(unsigned)blocks, SR_BLOCK, 0, st>>>(a, k, grad_out, d_image, d_depth, d_alpha);
+    image_reg_bwd_kernel<1><<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, k, grad_out, d_image, d_depth, d_alpha);
   return a3d_launch_status();
 }
 
@@ -374,10 +344,10 @@ extern "C" int a3d_gaussian_reg_f32(a3d_stream_t stream, int B, int N, const flo
   if (blocks == 0 || (!a.means && !a.scales && !a.scaling) || !partials || !out || !a3d_aligned(4, partials, out) || n_partials != blocks)
     return A3D_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  gauss_reg_fwd_kernel<<<(unsigned)blocks, SR_BLOCK, 0, st>>>(a, partials, n_partials);
+  gauss_reg_fwd_kernel<<<(unsigned)blocks, LR_BLOCK, 0, st>>>(a, partials, n_partials);
   // position: a mean over (B, N); the scale sum and the opacity term are sums
-  SrFinal f{3, {0, 1, 2, 0, 0}, {1.0 / ((double)B * (double)N), 1.0, 1.0, 0.0, 0.0}, {lambda_position, lambda_scales, lambda_opacity}};
-  sr_final_kernel<<<1, SR_BLOCK, 0, st>>>(partials, n_partials, f, out);
+  SrFinal<3> f{{0, 1, 2}, {1.0 / ((double)B * (double)N), 1.0, 1.0}, {lambda_position, lambda_scales, lambda_opacity}};
+  sr_final_kernel<3><<<1, LR_BLOCK, 0, st>>>(partials, n_partials, f, out);
   return a3d_launch_status();
 }
 
@@ -389,7 +359,7 @@ extern "C" int a3d_gaussian_reg_bwd_f32(a3d_stream_t stream, int B, int N, const
   // the backward reads no scales and no opacity: d_scales is a constant, d_opacity needs the log-scales only
   const int64_t blocks = gauss_reg_args(a, B, N, d_means ? means : nullptr, nullptr, 0, d_opacity ? scaling : nullptr, nullptr);
   if (blocks == 0 || !grad_out || !a3d_aligned(4, grad_out, d_means, d_scales, d_opacity)) return A3D_EINVAL;
-  gauss_reg_bwd_kernel<<<(unsigned)blocks, SR_BLOCK, 0, (hipStream_t)stream>>>(a, coef_position, coef_scales, coef_opacity, grad_out, d_means,
+  gauss_reg_bwd_kernel<<<(unsigned)blocks, LR_BLOCK, 0, (hipStream_t)stream>>>(a, coef_position, coef_scales, coef_opacity, grad_out, d_means,
                                                                               d_scales, d_opacity);
   return a3d_launch_status();
 }

@@ -1,5 +1,5 @@
 """The host layer shared by the fp32 4-D stage (``splat``, ``deform4d``, ``arap``, ``stage4d``): how its entry points are launched, what its inputs must
-be, how work cached per tensor is keyed, and the gather plan its atomic-free backward passes read.  No kernel of its own."""
+be, how work cached per tensor is keyed, the gather plan its atomic-free backward passes read, the workspace of its scalar losses.  No kernel of its own."""
 from __future__ import annotations
 
 import weakref
@@ -7,7 +7,7 @@ from typing import Tuple
 
 import torch
 
-from .hip_ops import _check, load_library
+from .hip_ops import _check, _p, load_library
 
 
 def launch(name: str, device: torch.device, *args):
@@ -15,6 +15,35 @@ def launch(name: str, device: torch.device, *args):
     ``args`` were allocated there, whichever device the caller has current.  A non-zero return code raises."""
     with torch.cuda.device(device):
         _check(getattr(load_library(), name)(torch.cuda.current_stream(device).cuda_stream, *args), name)
+
+
+def launch_reduced(name: str, device: torch.device, sizes, operands, n_sums: int, blocks, n_out: int) -> torch.Tensor:
+    """``launch`` for a forward entry point that ends in csrc/loss_reduce.h's reduction, ``name(stream, *sizes, *operands, partials,
+    n_partials, out)``.  ``blocks = (images, items, per_block)``: the entry point's grid is ``ceil(items / per_block)`` blocks per image.
+    The fp32 workspace ``partials [n_sums, n_partials]`` (a column per block) and the returned ``out [n_out]`` are allocated here."""
+    images, items, per_block = blocks
+    n_partials = images * ((items + per_block - 1) // per_block)
+    partials = torch.empty(n_sums, n_partials, dtype=torch.float32, device=device)
+    out = torch.empty(n_out, dtype=torch.float32, device=device)
+    launch(name, device, *sizes, *operands, _p(partials), n_partials, _p(out))
+    return out
+
+
+def require_shape(name: str, t, *shapes, non_empty: bool = False, optional: bool = False):
+    """``t`` is a tensor (``TypeError``) of one of ``shapes`` (``ValueError``; none given: of any shape).  A size is an int, or a name that
+    stands for any size; ``non_empty`` refuses a size of 0 as well, and ``optional`` lets ``None`` pass.  Device and dtype are
+    ``require_f32_cuda``'s to check."""
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+    have = tuple(t.shape)
+    if not shapes or (have in shapes and not (non_empty and 0 in have)):        # the usual case, without a walk over the sizes
+        return
+    fits = any(len(s) == len(have) and all(isinstance(want, str) or want == h for want, h in zip(s, have)) for s in shapes)
+    if not fits or (non_empty and 0 in have):
+        spelled = " or ".join("[" + ", ".join(map(str, s)) + "]" for s in shapes)
+        raise ValueError(f"{name}: expected {'a non-empty ' if non_empty else ''}{spelled}, got {list(have)}")
 
 
 def _require_cuda(name: str, t, dtypes, label: str):

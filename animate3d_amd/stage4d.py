@@ -19,10 +19,11 @@ is no torch fallback.
   with the clamp of advanced_4d.py:180; ``bg`` is one scalar because the reference uses ``back_ground_color[0]``);
   ``loss_mask = mean((alpha - m)^2)`` over ``B H W``, alpha unclamped (:183); ``loss = lambda_rgb loss_rgb + lambda_mask loss_mask``.
   All three are 0-d fp32; ``loss_rgb`` and ``loss_mask`` are detached (for logging): the gradient flows through ``loss`` only.
-* Summation has no atomics: two calls are bitwise equal.  The backward recomputes from the four inputs (no gradient buffer is kept: at
-  60 x 1024^2 it would be 1 GB): ``d_image = g (2 lambda_rgb / n_rgb)(c - y)`` where ``0 <= image <= 1`` and exactly 0 elsewhere (torch's
-  clamp rule), ``d_alpha = g (2 lambda_mask / n_mask)(alpha - m)``, in the planar layout the rasterizer's backward reads.  The upstream
-  gradient is read on the device: neither direction synchronises with the host.  Without a gradient to compute nothing is saved.
+* Summation has no atomics and one fixed order (csrc/loss_reduce.h): two calls are bitwise equal.  The backward recomputes from the
+  four inputs (no gradient buffer is kept: at 60 x 1024^2 it would be 1 GB): ``d_image = g (2 lambda_rgb / n_rgb)(c - y)`` where
+  ``0 <= image <= 1`` and exactly 0 elsewhere (torch's clamp rule), ``d_alpha = g (2 lambda_mask / n_mask)(alpha - m)``, in the planar
+  layout the rasterizer's backward reads.  The upstream gradient is read on the device: neither direction synchronises with the host.
+  Without a gradient to compute nothing is saved.
 
 ``image_regularizers(image, depth, alpha, *, lambda_tv, lambda_depth_tv, lambda_sparsity) -> (loss, tv, depth_tv, sparsity)`` and
 ``gaussian_regularizers(means, scales, scaling, opacity, *, lambda_position, lambda_scales, lambda_opacity) -> (loss, position, scale_sum,
@@ -57,7 +58,7 @@ import torch
 
 from .arap import ArapGraph, MeshGraph, arap_energy
 from .deform4d import HexPlaneDeformation
-from .f32_stage import launch, require_f32_cuda, require_index_cuda
+from .f32_stage import launch, launch_reduced, require_f32_cuda, require_index_cuda, require_shape
 from .hip_ops import _p
 from .splat import get_cam_info_gaussian, rasterize_gaussians
 
@@ -71,19 +72,23 @@ REG_ORDER = (("lambda_position", "loss_position"), ("lambda_opacity", "loss_opac
              ("lambda_scales", "loss_scales"), ("lambda_tv_loss", "loss_tv"), ("lambda_depth_tv_loss", "loss_depth_tv"))   # animate3d.py:256-296
 
 
-# ---- the loss kernel
+# ---- the loss kernels: a forward ends in csrc/loss_reduce.h's reduction (launch_reduced), a backward writes only the gradients asked for
+
+def _upstream(d_out):                                            # g[0]: the gradient of `loss`, which the kernel reads on the device
+    return d_out.detach().float().contiguous()
+
+
+def _empty_grads(need, shapes, device):                          # a gradient for the kernel to fill where needed, else None (NULL)
+    return [torch.empty(shape, dtype=torch.float32, device=device) if n else None for n, shape in zip(need, shapes)]
+
 
 class _MaskedReconLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, alpha, gt_rgb, gt_mask, index, bg, lambda_rgb, lambda_mask):
         B, _, H, W = image.shape
-        dev = image.device
         img, alp = image.detach().contiguous(), alpha.detach().contiguous()
-        n_partials = B * ((H * W + PIXELS_PER_BLOCK - 1) // PIXELS_PER_BLOCK)
-        partials = torch.empty(2, n_partials, dtype=torch.float32, device=dev)
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        launch("a3d_recon_loss_f32", dev, B, H, W, _p(img), _p(alp), _p(gt_rgb), _p(gt_mask), _p(index), bg, lambda_rgb, lambda_mask,
-               _p(partials), n_partials, _p(out))
+        out = launch_reduced("a3d_recon_loss_f32", image.device, (B, H, W), (_p(img), _p(alp), _p(gt_rgb), _p(gt_mask), _p(index), bg,
+                             lambda_rgb, lambda_mask), 2, (B, H * W, PIXELS_PER_BLOCK), 3)
         ctx.need = tuple(ctx.needs_input_grad[:2])
         if any(ctx.need):
             ctx.save_for_backward(img, alp, gt_rgb, gt_mask, index)
@@ -95,9 +100,8 @@ class _MaskedReconLoss(torch.autograd.Function):
         img, alp, gt_rgb, gt_mask, index = ctx.saved_tensors
         bg, coef_rgb, coef_mask, alpha_shape = ctx.consts
         B, _, H, W = img.shape
-        g = d_out.detach().float().contiguous()                  # g[0]: the gradient of `loss`; read on the device
-        d_image = torch.empty_like(img) if ctx.need[0] else None
-        d_alpha = torch.empty(alpha_shape, dtype=torch.float32, device=img.device) if ctx.need[1] else None
+        g = _upstream(d_out)
+        d_image, d_alpha = _empty_grads(ctx.need, (img.shape, alpha_shape), img.device)
         launch("a3d_recon_loss_bwd_f32", img.device, B, H, W, _p(img), _p(alp), _p(gt_rgb), _p(gt_mask), _p(index), bg, coef_rgb, coef_mask,
                _p(g), _p(d_image), _p(d_alpha))
         return d_image, d_alpha, None, None, None, None, None, None
@@ -111,18 +115,13 @@ def masked_recon_loss(image: torch.Tensor, alpha: torch.Tensor, gt_rgb: torch.Te
         raise TypeError(f"gt_mask: expected a bool or uint8 tensor, got {getattr(gt_mask, 'dtype', type(gt_mask))} (the tracked masks are "
                         "two-valued; threshold a soft mask first)")
     for name, t in (("image", image), ("alpha", alpha), ("gt_rgb", gt_rgb)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor, got {type(t)}")
-    if image.dim() != 4 or image.shape[1] != 3 or 0 in image.shape:
-        raise ValueError(f"image: expected a non-empty [B, 3, H, W], got {tuple(image.shape)}")
+        require_shape(name, t)                                   # tensors all three, before any shape is judged
+    require_shape("image", image, ("B", 3, "H", "W"), non_empty=True)
     B, _, H, W = image.shape
-    if tuple(alpha.shape) not in ((B, 1, H, W), (B, H, W)):
-        raise ValueError(f"alpha: expected {(B, 1, H, W)} or {(B, H, W)}, got {tuple(alpha.shape)}")
-    if gt_rgb.dim() != 4 or tuple(gt_rgb.shape[1:]) != (H, W, 3):
-        raise ValueError(f"gt_rgb: expected [S, {H}, {W}, 3], got {tuple(gt_rgb.shape)}")
+    require_shape("alpha", alpha, (B, 1, H, W), (B, H, W))
+    require_shape("gt_rgb", gt_rgb, ("S", H, W, 3))
     S = gt_rgb.shape[0]
-    if tuple(gt_mask.shape) not in ((S, H, W, 1), (S, H, W)):
-        raise ValueError(f"gt_mask: expected {(S, H, W, 1)} or {(S, H, W)}, got {tuple(gt_mask.shape)}")
+    require_shape("gt_mask", gt_mask, (S, H, W, 1), (S, H, W))
     if index is None and S != B:
         raise ValueError(f"index=None compares image b with frame b: needs S == B, got S = {S}, B = {B}")
     require_f32_cuda("image", image)
@@ -162,10 +161,7 @@ class _ImageReg(torch.autograd.Function):
         B, H, W = shape
         ops = [t.detach().contiguous() if lam != 0.0 else None for t, lam in zip((image, depth, alpha), lambdas)]
         dev = next(t for t in ops if t is not None).device
-        n_partials = B * ((H * W + REG_PIXELS_PER_BLOCK - 1) // REG_PIXELS_PER_BLOCK)
-        partials = torch.empty(5, n_partials, dtype=torch.float32, device=dev)
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        launch("a3d_image_reg_f32", dev, B, H, W, *(_p(t) for t in ops), *lambdas, _p(partials), n_partials, _p(out))
+        out = launch_reduced("a3d_image_reg_f32", dev, (B, H, W), (*(_p(t) for t in ops), *lambdas), 5, (B, H * W, REG_PIXELS_PER_BLOCK), 4)
         ctx.need = tuple(t is not None and need for t, need in zip(ops, ctx.needs_input_grad[:3]))
         if any(ctx.need):
             ctx.save_for_backward(*(t if need else None for t, need in zip(ops, ctx.need)))
@@ -179,8 +175,8 @@ class _ImageReg(torch.autograd.Function):
     def backward(ctx, d_out):
         ops = ctx.saved_tensors
         (B, H, W), coefs = ctx.consts
-        g = d_out.detach().float().contiguous()                  # g[0]: the gradient of `loss`; read on the device
-        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.need)]
+        g = _upstream(d_out)
+        grads = _empty_grads(ctx.need, (need and t.shape for t, need in zip(ops, ctx.need)), g.device)
         launch("a3d_image_reg_bwd_f32", g.device, B, H, W, *(_p(t) for t in ops), *coefs, _p(g), *(_p(t) for t in grads))
         return (*grads, None, None)
 
@@ -192,18 +188,10 @@ def image_regularizers(image: torch.Tensor, depth: Optional[torch.Tensor], alpha
     lambdas = (float(lambda_tv), float(lambda_depth_tv), float(lambda_sparsity))
     if not any(lambdas):
         raise ValueError("image_regularizers: every weight is 0, there is nothing to compute")
-    if not isinstance(image, torch.Tensor):
-        raise TypeError(f"image: expected a tensor, got {type(image)}")
-    if image.dim() != 4 or image.shape[1] != 3 or 0 in image.shape:
-        raise ValueError(f"image: expected a non-empty [B, 3, H, W], got {tuple(image.shape)}")
+    require_shape("image", image, ("B", 3, "H", "W"), non_empty=True)
     B, _, H, W = image.shape
-    for name, t, lam, shapes in (("depth", depth, lambdas[1], ((B, 1, H, W),)), ("alpha", alpha, lambdas[2], ((B, 1, H, W), (B, H, W)))):
-        if t is None and lam == 0.0:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a tensor, got {type(t)}")
-        if tuple(t.shape) not in shapes:
-            raise ValueError(f"{name}: expected {' or '.join(map(str, shapes))}, got {tuple(t.shape)}")
+    require_shape("depth", depth, (B, 1, H, W), optional=lambdas[1] == 0.0)
+    require_shape("alpha", alpha, (B, 1, H, W), (B, H, W), optional=lambdas[2] == 0.0)
     if (lambdas[0] or lambdas[1]) and (H < 2 or W < 2):
         raise ValueError(f"a total-variation term needs H >= 2 and W >= 2, got {H} x {W} (the reference divides by zero)")
     for name, t in (("image", image), ("depth", depth), ("alpha", alpha)):
@@ -227,10 +215,8 @@ class _GaussianReg(torch.autograd.Function):
             sc, scales_bs = (scales[0].detach(), 0) if shared else (scales.detach().contiguous(), 3 * N)
         sg, op = (scaling.detach().contiguous(), opacity.detach().contiguous()) if l_op else (None, None)
         dev = next(t for t in (m, sc, sg) if t is not None).device
-        n_partials = (B * N + REG_PAIRS_PER_BLOCK - 1) // REG_PAIRS_PER_BLOCK
-        partials = torch.empty(3, n_partials, dtype=torch.float32, device=dev)
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        launch("a3d_gaussian_reg_f32", dev, B, N, _p(m), _p(sc), scales_bs, _p(sg), _p(op), *lambdas, _p(partials), n_partials, _p(out))
+        out = launch_reduced("a3d_gaussian_reg_f32", dev, (B, N), (_p(m), _p(sc), scales_bs, _p(sg), _p(op), *lambdas), 3,
+                             (1, B * N, REG_PAIRS_PER_BLOCK), 4)
         need = ctx.needs_input_grad
         ctx.need = (bool(l_pos) and need[0], bool(l_sc) and need[1], bool(l_op) and need[3])
         if any(ctx.need):
@@ -242,10 +228,8 @@ class _GaussianReg(torch.autograd.Function):
     def backward(ctx, d_out):
         m, sg = ctx.saved_tensors
         (B, N), coefs, opacity_shape, dev = ctx.consts
-        g = d_out.detach().float().contiguous()
-        d_means = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if ctx.need[0] else None
-        d_scales = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if ctx.need[1] else None
-        d_opacity = torch.empty(opacity_shape, dtype=torch.float32, device=dev) if ctx.need[2] else None
+        g = _upstream(d_out)
+        d_means, d_scales, d_opacity = _empty_grads(ctx.need, ((B, N, 3), (B, N, 3), opacity_shape), dev)
         launch("a3d_gaussian_reg_bwd_f32", dev, B, N, _p(m), _p(sg), *coefs, _p(g), _p(d_means), _p(d_scales), _p(d_opacity))
         return d_means, d_scales, None, d_opacity, None, None
 
@@ -260,17 +244,13 @@ def gaussian_regularizers(means: Optional[torch.Tensor], scales: Optional[torch.
         raise ValueError("gaussian_regularizers: every weight is 0, there is nothing to compute")
     given = [("means", means, lambdas[0]), ("scales", scales, lambdas[1]), ("scaling", scaling, lambdas[2]), ("opacity", opacity, lambdas[2])]
     for name, t, lam in given:
-        if not (isinstance(t, torch.Tensor) or (t is None and lam == 0.0)):
-            raise TypeError(f"{name}: expected a tensor, got {type(t)}")
+        require_shape(name, t, optional=lam == 0.0)              # tensors (or None at weight 0) all four, before any shape is judged
+    require_shape("means", means, ("B", "N", 3), non_empty=True, optional=True)
+    require_shape("scales", scales, ("B", "N", 3) if means is None else tuple(means.shape), non_empty=True, optional=True)
     per_image = [t for t in (means, scales) if t is not None]
-    for name, t in (("means", means), ("scales", scales)):
-        if t is not None and (t.dim() != 3 or t.shape[2] != 3 or 0 in t.shape or t.shape != per_image[0].shape):
-            raise ValueError(f"{name}: expected a non-empty [B, N, 3]{' like means' if name == 'scales' else ''}, got {tuple(t.shape)}")
     B, N = per_image[0].shape[:2] if per_image else (1, scaling.shape[0] if scaling.dim() else 0)
-    if scaling is not None and (tuple(scaling.shape) != (N, 3) or N == 0):
-        raise ValueError(f"scaling: expected a non-empty [{N}, 3], got {tuple(scaling.shape)}")
-    if opacity is not None and tuple(opacity.shape) not in ((N, 1), (N,)):
-        raise ValueError(f"opacity: expected {(N, 1)} or {(N,)}, got {tuple(opacity.shape)}")
+    require_shape("scaling", scaling, (N, 3), non_empty=True, optional=True)
+    require_shape("opacity", opacity, (N, 1), (N,), optional=True)
     for name, t, _ in given:
         if t is not None:
             require_f32_cuda(name, t)
