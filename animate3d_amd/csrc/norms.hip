@@ -300,10 +300,45 @@ inline bool gn_fused_plan(int64_t rows, int C, int groups, GNFPlan& out) {
   return 8 * out.nx <= out.threads && out.sg <= out.threads;
 }
 
+// Which kernels a whole GroupNorm (mode 0) of this geometry runs, and with what shape: the ONE place that decides it.  group_norm_launch
+// launches from it and a3d_group_norm_plan reports it, so a test that takes its probe rows from the query probes the launch that runs.
+struct GNDispatch {
+  bool fused;        // gn_fused_kernel; false: gn_partial / gn_finalize / gn_apply with block(nx, ny)
+  GNFPlan pl;        // fused only
+  int rmax;          // fused only: the kernel instantiation's chunks per thread (11 or 21)
+  bool stream;       // fused only: non-temporal accesses (full-line slabs of a one-source input)
+  int nx, ny;        // thread layout: chunk columns x row lanes (fused: of the plan)
+};
+inline int gn_fused_rmax(int iters) { return iters <= 11 ? 11 : 21; }
+inline int gn_three_launch_ny(int C) { int ny = 256 / (C / 8); if (ny < 1) ny = 1; if (ny > 32) ny = 32; return ny; }
+// (no condition on B: B <= 65535 and nslab <= groups <= 1024 keep the grid's B * nslab far below 2^31)
+inline GNDispatch gn_dispatch(int64_t rows, int C, int groups, bool two_source) {
+  GNDispatch d{};
+  if (gn_fused_plan(rows, C, groups, d.pl) && rows * (int64_t)C * 2 < (1ll << 31)) {
+    d.fused = true;
+    d.rmax = gn_fused_rmax(d.pl.iters);
+    d.stream = (d.pl.sg * (C / groups) * 2) % 128 == 0 && !two_source;      // (every slab then starts on a line: C % (sg cg) == 0)
+    d.nx = d.pl.nx; d.ny = d.pl.ny;
+    return d;
+  }
+  d.nx = C / 8; d.ny = gn_three_launch_ny(C);
+  return d;
+}
+// geometry every GroupNorm entry point accepts (the pointer checks are the caller's)
+inline bool gn_geometry_ok(int64_t rows, int C, int groups) {
+  if (rows <= 0 || C <= 0 || groups <= 0) return false;
+  if (C % 8 != 0 || C % groups != 0 || C / 8 > 1024 || groups > 1024) return false;
+  // a 16-byte chunk (8 channels) must touch at most 2 groups: channels-per-group 4 (chunk = exactly 2 groups) or >= 7
+  // (8 channels starting anywhere span <= 2 groups of >= 7); 5 and 6 can straddle 3 groups and are rejected
+  if (const int cg = C / groups; cg < 4 || cg == 5 || cg == 6) return false;
+  return true;
+}
+
 template <bool STREAM>
-void gn_fused_launch(const GNParams& p, const GNFPlan& pl, int B, size_t smem, hipStream_t s) {
+void gn_fused_launch(const GNParams& p, const GNDispatch& d, int B, size_t smem, hipStream_t s) {
+  const GNFPlan& pl = d.pl;
   const dim3 grid((unsigned)(B * pl.nslab)), block(pl.threads);
-  if (pl.iters <= 11) gn_fused_kernel<STREAM, 11><<<grid, block, smem, s>>>(p, pl.sg, pl.nx, pl.ny, pl.nslab);
+  if (d.rmax == 11) gn_fused_kernel<STREAM, 11><<<grid, block, smem, s>>>(p, pl.sg, pl.nx, pl.ny, pl.nslab);
   else gn_fused_kernel<STREAM, 21><<<grid, block, smem, s>>>(p, pl.sg, pl.nx, pl.ny, pl.nslab);
 }
 
@@ -504,20 +539,25 @@ inline int gn_nchunk(int64_t rows) { return (int)((rows + GN_ROWS_PER_BLOCK - 1)
 extern "C" int64_t a3d_group_norm_ws_floats(int B, int64_t rows, int groups) {
   return (int64_t)B * gn_nchunk(rows) * groups * 2 + (int64_t)B * groups * 2;
 }
+
+extern "C" int a3d_group_norm_plan(int64_t rows, int C, int groups, int* out) {
+  if (!out || !gn_geometry_ok(rows, C, groups)) return A3D_EINVAL;
+  const GNDispatch d = gn_dispatch(rows, C, groups, false);
+  if (!d.fused && d.nx * d.ny < groups) return A3D_EINVAL;
+  out[0] = d.fused ? 1 : 0; out[1] = d.fused ? d.pl.sg : 0; out[2] = d.nx; out[3] = d.ny;
+  out[4] = d.fused ? d.pl.threads : d.nx * d.ny; out[5] = d.rmax; out[6] = d.fused ? (d.stream ? 1 : 0) : 1;
+  return 0;
+}
 #endif
 
 // mode 0: whole GroupNorm; 1: statistics only (raw fp64 sums); 2: apply only (stats = [B][groups][2] mean, rstd)
 static int group_norm_launch(int mode, a3d_stream_t stream, const void* X, void* Y, const float* gamma, const float* beta,
                              float* ws, double* sums, const float* stats_in, int B, int64_t rows, int C, int groups, float eps, int silu,
                              const void* Xb = nullptr, int C1 = 0) {
-  if (!X || B <= 0 || rows <= 0 || C <= 0 || groups <= 0) return A3D_EINVAL;
+  if (!X || B <= 0 || !gn_geometry_ok(rows, C, groups)) return A3D_EINVAL;
   if (Xb && (C1 <= 0 || C1 >= C || C1 % 8 != 0 || (reinterpret_cast<uintptr_t>(Xb) & 15u))) return A3D_EINVAL;
   if (mode != 1 && (!Y || !gamma || !beta)) return A3D_EINVAL;
   if ((mode != 2 && !ws) || (mode == 1 && !sums) || (mode == 2 && !stats_in)) return A3D_EINVAL;
-  if (C % 8 != 0 || C % groups != 0 || C / 8 > 1024 || groups > 1024) return A3D_EINVAL;
-  // a 16-byte chunk (8 channels) must touch at most 2 groups: channels-per-group 4 (chunk = exactly 2 groups) or >= 7
-  // (8 channels starting anywhere span <= 2 groups of >= 7); 5 and 6 can straddle 3 groups and are rejected
-  if (const int cg = C / groups; cg < 4 || cg == 5 || cg == 6) return A3D_EINVAL;
   if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
   if (B > 65535) return A3D_EINVAL;
   GNParams p{};
@@ -528,18 +568,15 @@ static int group_norm_launch(int mode, a3d_stream_t stream, const void* X, void*
   p.partial = ws; p.stats = mode == 2 ? const_cast<float*>(stats_in) : ws + (int64_t)B * p.nchunk * groups * 2;
   p.sums = mode == 1 ? sums : nullptr;
   hipStream_t s = (hipStream_t)stream;
-  if (mode == 0) {
-    GNFPlan pl;
-    if (gn_fused_plan(rows, C, groups, pl) && (int64_t)B * pl.nslab <= 0x7fffffffLL && rows * (int64_t)C * 2 < (1ll << 31)) {
-      const size_t smem = ((size_t)pl.ny * pl.nx * 4 + (size_t)8 * pl.nx * 4 + (size_t)2 * pl.sg) * sizeof(float);
-      const bool full_lines = (pl.sg * p.cg * 2) % 128 == 0 && Xb == nullptr;      // (every slab then starts on a line: C % (sg cg) == 0)
-      if (full_lines) gn_fused_launch<true>(p, pl, B, smem, s);
-      else gn_fused_launch<false>(p, pl, B, smem, s);
-      return a3d_launch_status();
-    }
+  const GNDispatch d = gn_dispatch(rows, C, groups, Xb != nullptr);
+  if (mode == 0 && d.fused) {
+    const GNFPlan& pl = d.pl;
+    const size_t smem = ((size_t)pl.ny * pl.nx * 4 + (size_t)8 * pl.nx * 4 + (size_t)2 * pl.sg) * sizeof(float);
+    if (d.stream) gn_fused_launch<true>(p, d, B, smem, s);
+    else gn_fused_launch<false>(p, d, B, smem, s);
+    return a3d_launch_status();
   }
-  const int c8 = C / 8;
-  int ny = 256 / c8; if (ny < 1) ny = 1; if (ny > 32) ny = 32;
+  const int c8 = C / 8, ny = gn_three_launch_ny(C);
   if (c8 * ny < groups) return A3D_EINVAL;
   const dim3 block(c8, ny), grid(p.nchunk, B);
   if (mode != 2) {
@@ -579,6 +616,7 @@ extern "C" int A3D_FN(a3d_layer_norm)(a3d_stream_t stream, const void* X, void* 
   if (!X || !Y1 || !gamma || !beta || M <= 0 || C <= 0 || C % 8 != 0 || C > 1536) return A3D_EINVAL;
   if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y1) | reinterpret_cast<uintptr_t>(Y2)) & 15u) return A3D_EINVAL;
   if ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15u) return A3D_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(pe1) | reinterpret_cast<uintptr_t>(pe2)) & 15u) return A3D_EINVAL;      // (read 16 bytes at a time)
   if ((pe1 && (pe1_div <= 0 || pe1_mod <= 0)) || (pe2 && (pe2_div <= 0 || pe2_mod <= 0))) return A3D_EINVAL;
   LNParams p{};
   p.X = (const uint16_t*)X; p.Y1 = (uint16_t*)Y1; p.Y2 = (uint16_t*)Y2; p.gamma = gamma; p.beta = beta;

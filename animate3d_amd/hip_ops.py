@@ -75,6 +75,7 @@ _SIGNATURES = {
     "a3d_temporal_attn_sharded_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_i64, c_int, c_int, c_f32,
                                                c_int, c_int, c_int, c_i64]),
     "a3d_group_norm_ws_floats": (c_i64, [c_int, c_i64, c_int]),
+    "a3d_group_norm_plan": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_int)]),
     "a3d_group_norm_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_f32, c_int]),
     "a3d_group_norm2_bf16": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_f32, c_int]),
     "a3d_group_norm_sums_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int]),
@@ -179,6 +180,19 @@ def load_library():
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
+
+
+GN_PLAN_FIELDS = ("fused", "sg", "nx", "ny", "threads", "rmax", "stream")
+
+
+def group_norm_plan(rows: int, C: int, groups: int) -> dict:
+    """How a3d_group_norm runs a one-source instance (a3d_group_norm_plan: host only, needs no GPU): the fields of GN_PLAN_FIELDS, plus
+    ``iters`` = rows a thread of the one-launch kernel owns at most."""
+    out = (c_int * len(GN_PLAN_FIELDS))()
+    _check(load_library().a3d_group_norm_plan(rows, C, groups, out), f"a3d_group_norm_plan rows={rows} C={C} groups={groups}")
+    plan = dict(zip(GN_PLAN_FIELDS, out))
+    plan["iters"] = -(-rows // plan["ny"]) if plan["fused"] else 0
+    return plan
 
 
 def _check(rc: int, what: str):

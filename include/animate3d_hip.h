@@ -202,6 +202,15 @@ int64_t a3d_group_norm_ws_floats(int B, int64_t rows, int groups);
 int a3d_group_norm_bf16(a3d_stream_t stream, const void* X, void* Y, const float* gamma, const float* beta,
                         float* ws, int B, int64_t rows, int C, int groups, float eps, int silu);
 
+/* Host-only query (touches no GPU): how a3d_group_norm_{bf16,f16} runs a one-source instance of this geometry.  The launch decides from the
+ * same code.  out[7] = { fused, sg, nx, ny, threads, rmax, stream }:
+ *   fused 1: one launch, a workgroup keeps a slab of `sg` whole groups in registers: `threads` threads = nx 16-byte chunk columns x ny row
+ *            lanes (a thread owns rows ry, ry + ny, ...: at most rmax = 11 or 21 of them); stream 1: non-temporal accesses (a two-source
+ *            input, a3d_group_norm2, never streams);
+ *   fused 0: three launches (partial sums, finalize, apply) of blocks (nx = C / 8, ny) over 128-row chunks; sg = rmax = 0, stream = 1.
+ * Returns A3D_EINVAL for a geometry a3d_group_norm refuses (or out == NULL), 0 otherwise. */
+int a3d_group_norm_plan(int64_t rows, int C, int groups, int* out);
+
 /* a3d_group_norm_bf16 over a TWO-SOURCE input: channels [0, Ca) of a row come from Xa ([B*rows, Ca]), channels [Ca, Ca + Cb) from Xb
  * ([B*rows, Cb]); Y is the normalised [B*rows, Ca + Cb] tensor.  norm1 of an up-block ResnetBlock2D over torch.cat([hidden, skip], dim=1)
  * (diffusers CrossAttnUpBlockMotion / UpBlockMotion, unet_motion_mv_model.py:826-827) without the concatenation pass (round 5).  A group may
@@ -220,7 +229,8 @@ int a3d_group_norm_apply_bf16(a3d_stream_t stream, const void* X, void* Y, const
 /* LayerNorm over C, with the positional-embedding adds of the motion-module processor fused:
  *   Y1[m] = LN(X[m]) + pe1[(m / pe1_div) % pe1_mod]     (pe1 may be NULL)
  *   Y2[m] = LN(X[m]) + pe2[(m / pe2_div) % pe2_mod]     (Y2 may be NULL)
- * (time_pos_embed attention_processor.py:583-584; SinePositionalEncoding2D :561-563). */
+ * (time_pos_embed attention_processor.py:583-584; SinePositionalEncoding2D :561-563).
+ * X, Y1, Y2, gamma, beta, pe1 and pe2 are accessed 16 bytes at a time: one that is not 16-byte aligned is A3D_EINVAL. */
 int a3d_layer_norm_bf16(a3d_stream_t stream, const void* X, void* Y1, void* Y2, const float* gamma,
                         const float* beta, int64_t M, int C, float eps,
                         const void* pe1, int64_t pe1_div, int64_t pe1_mod,

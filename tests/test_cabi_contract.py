@@ -3,8 +3,8 @@ the widest access the kernels make through it, or an attention-backward do_scale
 A3D_EINVAL before anything reaches the GPU.  The device addresses below are made up and never dereferenced: every call differs from a
 valid launch in exactly one operand, and the argument checks run before the first HIP call, so this runs on a machine without a GPU.
 (No call here may pass with every pointer aligned: that would launch a kernel on made-up addresses.)  The forward attention entry
-points, the deformation field's (a3d_dg_*), the ARAP loss's (a3d_knn_f32, a3d_arap_*) and the splat rasterizer's (a3d_gs_*) are held to
-the same discipline further down."""
+points, the deformation field's (a3d_dg_*), the ARAP loss's (a3d_knn_f32, a3d_arap_*), the splat rasterizer's (a3d_gs_*) and the forward
+normalisations (a3d_group_norm*, a3d_layer_norm) are held to the same discipline further down."""
 import ctypes
 import math
 
@@ -514,3 +514,77 @@ def test_splat_tile_ranges_and_sum_batch_refusals(lib):
     assert _gs_call(lib, "a3d_gs_tile_ranges_f32", ptr=dict(ranges=None), L=0) == A3D_EINVAL
     for g in (dict(sumB=0), dict(sumB=-1), dict(sumM=0), dict(sumM=-1)):
         assert _gs_call(lib, "a3d_gs_sum_batch_f32", **g) == A3D_EINVAL, g
+
+
+# ---- forward normalisation (a3d_group_norm, _group_norm2, _group_norm_sums, _group_norm_apply, a3d_layer_norm: csrc/norms.hip)
+NORM_VALID = dict(B=2, rows=64, C=320, Ca=192, Cb=128, groups=32, M=64, pe1_div=4, pe1_mod=3, pe2_div=1, pe2_mod=5)
+# entry point -> operands in argument order; every one of them is accessed 16 bytes at a time except the fp32 / fp64 arrays of GroupNorm
+NORM_OPERANDS = {
+    "a3d_group_norm_bf16": ("X", "Y", "gamma", "beta", "ws"),
+    "a3d_group_norm2_bf16": ("X", "Xb", "Y", "gamma", "beta", "ws"),
+    "a3d_group_norm_sums_bf16": ("X", "ws", "sums"),
+    "a3d_group_norm_apply_bf16": ("X", "Y", "gamma", "beta", "stats"),
+    "a3d_layer_norm_bf16": ("X", "Y1", "Y2", "gamma", "beta", "pe1", "pe2"),
+}
+NORM_ALIGN16 = {"a3d_group_norm_bf16": ("X", "Y"), "a3d_group_norm2_bf16": ("X", "Xb", "Y"), "a3d_group_norm_sums_bf16": ("X",),
+                "a3d_group_norm_apply_bf16": ("X", "Y"), "a3d_layer_norm_bf16": ("X", "Y1", "Y2", "gamma", "beta", "pe1", "pe2")}
+NORM_REQUIRED = {"a3d_group_norm_bf16": ("X", "Y", "gamma", "beta", "ws"), "a3d_group_norm2_bf16": ("X", "Xb", "Y", "gamma", "beta", "ws"),
+                 "a3d_group_norm_sums_bf16": ("X", "ws", "sums"), "a3d_group_norm_apply_bf16": ("X", "Y", "gamma", "beta", "stats"),
+                 "a3d_layer_norm_bf16": ("X", "Y1", "gamma", "beta")}          # Y2, pe1, pe2 may be NULL: such a call would launch
+
+
+def _norm_call(lib, entry, f16, ptr=None, **geometry):
+    """The valid launch of `entry` (GroupNorm: 2 x 64 rows x 320 channels in 32 groups, two-source 192 + 128; LayerNorm: 64 x 320 with
+    both embedding maps) with the named pointers / geometry words replaced.  Callers replace exactly one, and never none."""
+    assert ptr or geometry, "a fully valid call would launch a kernel on made-up addresses"
+    p = _ptrs(NORM_OPERANDS[entry])
+    p.update(ptr or {})
+    g = dict(NORM_VALID, **geometry)
+    if entry == "a3d_group_norm_bf16":
+        args = [None, p["X"], p["Y"], p["gamma"], p["beta"], p["ws"], g["B"], g["rows"], g["C"], g["groups"], 1e-5, 1]
+    elif entry == "a3d_group_norm2_bf16":
+        args = [None, p["X"], g["Ca"], p["Xb"], g["Cb"], p["Y"], p["gamma"], p["beta"], p["ws"], g["B"], g["rows"], g["groups"], 1e-5, 1]
+    elif entry == "a3d_group_norm_sums_bf16":
+        args = [None, p["X"], p["ws"], p["sums"], g["B"], g["rows"], g["C"], g["groups"]]
+    elif entry == "a3d_group_norm_apply_bf16":
+        args = [None, p["X"], p["Y"], p["gamma"], p["beta"], p["stats"], g["B"], g["rows"], g["C"], g["groups"], 1]
+    else:
+        args = [None, p["X"], p["Y1"], p["Y2"], p["gamma"], p["beta"], g["M"], g["C"], 1e-5, p["pe1"], g["pe1_div"], g["pe1_mod"],
+                p["pe2"], g["pe2_div"], g["pe2_mod"]]
+    return getattr(lib, _twin(entry, f16))(*args)
+
+
+NORM = pytest.mark.parametrize("entry", sorted(NORM_OPERANDS))
+
+
+@F16
+@NORM
+def test_forward_norms_refuse_misaligned_or_missing_operand(lib, entry, f16):
+    """X, Y, Xb of the GroupNorm entry points and every operand of a3d_layer_norm (pe1 / pe2 included: the embedding rows are read 16 bytes
+    at a time) 8 bytes off; every required operand NULL (the workspace, the sums and the statistics among them)."""
+    base = _ptrs(NORM_OPERANDS[entry])
+    for operand in NORM_ALIGN16[entry]:
+        rc = _norm_call(lib, entry, f16, ptr={operand: base[operand] + 8})
+        assert rc == A3D_EINVAL, f"{entry}: {operand} at +8 bytes returned {rc}"
+    for operand in NORM_REQUIRED[entry]:
+        rc = _norm_call(lib, entry, f16, ptr={operand: None})
+        assert rc == A3D_EINVAL, f"{entry}: NULL {operand} returned {rc}"
+
+
+@F16
+@NORM
+def test_forward_norms_refuse_bad_geometry(lib, entry, f16):
+    """GroupNorm: channels-per-group 5 and 6 (a 16-byte chunk could touch three groups), C % 8, more than 1024 groups, B > 65535, empty
+    extents; two-source: C1 % 8 and C1 outside (0, C).  LayerNorm: C % 8, C > 1536, pe_div / pe_mod <= 0, M <= 0."""
+    if entry == "a3d_layer_norm_bf16":
+        bad = [dict(C=324), dict(C=1544), dict(C=2048), dict(C=0), dict(M=0), dict(M=-1),
+               dict(pe1_div=0), dict(pe1_div=-4), dict(pe1_mod=0), dict(pe1_mod=-3), dict(pe2_div=0), dict(pe2_div=-1), dict(pe2_mod=0), dict(pe2_mod=-5)]
+    elif entry == "a3d_group_norm2_bf16":
+        bad = [dict(Ca=196, Cb=124), dict(Ca=0, Cb=320), dict(Ca=320, Cb=0), dict(Ca=-8, Cb=328), dict(Ca=328, Cb=-8),
+               dict(Ca=96, Cb=64), dict(Ca=128, Cb=64), dict(Ca=192, Cb=132), dict(Ca=8 * 1100, Cb=8 * 1100, groups=1100),
+               dict(B=65536), dict(B=0), dict(rows=0), dict(groups=0), dict(groups=33)]          # 160 / 32 = 5, 192 / 32 = 6
+    else:
+        bad = [dict(C=160), dict(C=192), dict(C=324), dict(C=8 * 1100, groups=1100), dict(C=96, groups=32), dict(B=65536), dict(B=0), dict(rows=0),
+               dict(C=0), dict(groups=0), dict(groups=33), dict(C=8 * 1032, groups=8)]          # cg = 5, 6, 3; C / 8 > 1024
+    for g in bad:
+        assert _norm_call(lib, entry, f16, **g) == A3D_EINVAL, f"{entry}: {g}"

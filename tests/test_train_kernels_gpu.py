@@ -162,10 +162,12 @@ def test_layer_norm_bwd(ops, ref, M, C):
     check(f"layer_norm_bwd dx (no parameter gradients) {M}x{C}", dx2, rx, ELEM_TOL[dt])
 
 
-@pytest.mark.parametrize("M,C", [(4099, 320), (1030, 640), (515, 1280)])
+@pytest.mark.parametrize("M,C", [(4099, 320), (1030, 640), (515, 1280), (16391, 320), (4099, 1280), (32771, 1280)])
 def test_layer_norm_bwd_sub_wave_rows_kernel_tail_and_grid_stride(ops, ref, M, C):
     """C = 40 * LPR: LPR lanes per row, 64 / LPR rows per wave step; M is not a multiple of the rows per step (masked tail rows must not
-    reach dgamma / dbeta) and, with parameter gradients, large enough that the <= 512 workgroups loop."""
+    reach dgamma / dbeta).  The first three shapes launch 129, 65 and 65 workgroups and never loop; 16391 x 320 and 4099 x 1280 are 513
+    workgroups' worth of row batches, so with parameter gradients the <= 512 workgroups loop, and 32771 x 1280 is 4097 workgroups' worth,
+    so the <= 4096 of the frozen-affine launch loop too."""
     dt = ops.act_dtype
     x, dy = rnd(M, C, seed=11, scale=1.5, dtype=dt) + 0.25, rnd(M, C, seed=12, dtype=dt)
     gamma = 1.0 + 0.2 * rnd(C, seed=13)
