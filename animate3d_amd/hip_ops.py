@@ -137,6 +137,10 @@ _SIGNATURES = {
     "a3d_arap_energy_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_arap_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_mesh_sample_neighbours": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
+    # mesh ingest (csrc/mesh_ingest.hip): fp32 only, no storage twins; rot9 / quat4 are host pointers to doubles
+    "a3d_mesh_vertex_gaussians_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
+                                              c_int, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_gaussians_rigid_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     # reconstruction loss of the 4-D stage (csrc/recon_loss.hip): fp32 only, no storage twins
     "a3d_recon_loss_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_recon_loss_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),

@@ -510,6 +510,35 @@ int a3d_arap_backward_f32(a3d_stream_t stream, int F, int Nv, int K, int S, cons
 int a3d_mesh_sample_neighbours(a3d_stream_t stream, int Nv, int E, const int* row_start, const int* col, int K, const int64_t* seed,
                                int* nn_idx);
 
+/* Mesh ingest (csrc/mesh_ingest.hip; contract in animate3d_amd/mesh.py), fp32 at the interface.  Replaces the Python loops of
+ * tools/mesh_animation/mesh2gaussian.py and the transform of Gaussian4DModel.load_ply (geometry/gaussian_4d.py:177-260).  rot9 (R,
+ * row-major) and quat4 (R's unit quaternion w, x, y, z) are HOST pointers to doubles, read before the launch; every other pointer is
+ * device memory, 4-byte aligned.
+ *   a3d_mesh_vertex_gaussians_f32  one thread per vertex of verts [Nv, 3] over the CSR adjacency row_start [Nv + 1] / col [E] (col and
+ *                          edge_length may be NULL when E = 0): edge_length [E] = |x_v - x_col[e]| for e in v's row; mean_edge [Nv, 3] =
+ *                          the sum over the row, in row order, of |x_u - x_v| per axis, divided by the degree (0 for an empty row);
+ *                          colors [Nv, 3] = vertex_colors [Nv, 3] as they are, or the sum over v's corners, in the order of the list
+ *                          corner_order [C] / corner_start [Nv + 1] (corner k is entry k of faces [F, 3] flattened, C = 3 F), of the
+ *                          corner's colour, divided by their number: corner_colors [C, 3], or texture [Ht, Wt, 3] sampled bilinearly
+ *                          at uvs [Nt, 2][corner_uv [C]] with the v axis flipped, pixel centres at the ends of [0, 1] and the
+ *                          coordinates clamped to it (grid_sample with align_corners and border padding on the row-flipped texture).
+ *                          xyz = scale_factor R x, scaling = log(mean_edge / shrink * scale_factor) (-inf for a zero), shs =
+ *                          (colors - 0.5) / 0.28209479177387814.  Exactly one of vertex_colors, corner_colors and texture is not NULL.
+ *                          A3D_EINVAL before any launch for: a NULL required pointer, Nv <= 0, E < 0, zero or several colour sources,
+ *                          a corner source without its list or with C < 1, Ht / Wt / Nt < 1, shrink or scale_factor not a positive
+ *                          finite number, a misaligned pointer.  Row bounds and the indices the kernel reads (col, corner_order,
+ *                          corner_uv) are clamped to their arrays.  No atomics, no workspace, one launch
+ *   a3d_gaussians_rigid_f32  N Gaussians: xyz = scale_factor R xyz_in, scaling = scaling_in + log(scale_factor), rotation =
+ *                          q_R (x) rotation_in / |rotation_in| (Hamilton product, w first), in fp64 with one rounding.  A3D_EINVAL for
+ *                          a NULL pointer, N <= 0, scale_factor not a positive finite number, a misaligned pointer.  In place is fine */
+int a3d_mesh_vertex_gaussians_f32(a3d_stream_t stream, int Nv, int E, int C, const float* verts, const int* row_start, const int* col,
+                                  const int* corner_order, const int* corner_start, const float* vertex_colors, const float* corner_colors,
+                                  const float* texture, int Ht, int Wt, const float* uvs, int Nt, const int* corner_uv, const double* rot9,
+                                  double scale_factor, double shrink, float* xyz, float* scaling, float* shs, float* colors,
+                                  float* mean_edge, float* edge_length);
+int a3d_gaussians_rigid_f32(a3d_stream_t stream, int N, const float* xyz_in, const float* scaling_in, const float* rotation_in,
+                            const double* rot9, const double* quat4, double scale_factor, float* xyz, float* scaling, float* rotation);
+
 /* Reconstruction loss of the 4-D stage (csrc/recon_loss.hip; contract in animate3d_amd/stage4d.py, masked_recon_loss), fp32.  Replaces the
  * val[sampled_idx] copies, the mask compositing and the two F.mse_loss of custom/threestudio-animate3d/systems/animate3d.py:160-184 and the
  * clamp of diff_gaussian_rasterizer_advanced_4d.py:180.  image [B, 3, H, W] planar and unclamped, alpha [B, H, W], gt_rgb [S, H, W, 3]
