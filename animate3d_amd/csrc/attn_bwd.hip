@@ -28,6 +28,20 @@ namespace {
 
 constexpr int MODE_DQ = 0, MODE_DKV = 1, MODE_STATS = 2;
 
+// Gradient store, 8 bytes per access in the accumulators' own layout: the 32x32 transposed-gradient tiles leave lane (l31, half g) with
+// dX[col = l31][d = 32 mt + 8 qd + 4 g + j] in register 4 qd + j of tile mt; `orow` is the lane's row at its head, `val(mt, r)` the
+// finished float of register r of tile mt.
+template <int D, int MT, typename F>
+A3D_DEV void store_acc8(uint16_t* orow, int g, bool accumulate, F&& val) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int d = 32 * mt + 8 * qd + 4 * g;
+      if (d < D) store4(orow + d, accumulate, val(mt, 4 * qd), val(mt, 4 * qd + 1), val(mt, 4 * qd + 2), val(mt, 4 * qd + 3));
+    }
+}
+
 struct BwdParams {
   const uint16_t* Q; const uint16_t* K; const uint16_t* V; const uint16_t* dO;
   uint16_t* dQ; uint16_t* dK; uint16_t* dV;

@@ -39,15 +39,9 @@
 
 namespace {
 
-// VAR (tuning experiments, a3d_tune_flash): 1 = s_setprio(1) around MFMA groups, 2 = V fragments read before the
-// exps of their sub-tile, 4 = sched_group_barrier pattern {1 MFMA, 4 TRANS, 2 VALU} over the exp/PV section.
-// NM = 1 (bf16 storage, OFS_PAD / OFS_ACC, aligned launches without a tail, >= 3 tiles): first a max-free pass — the offset is the exact
-// maximum of the first tile + 40 and never moves (bf16 P has fp32's exponent range; fp32 accumulation), so the per-score VALU work is
-// one v_exp and half a v_cvt_pk; the row sums out of the matrix pipe are checked once at the end and a workgroup whose sums
-// left [0, 2^100) re-runs with the exact lazy running maximum (flash_attn_dm.hip has the long form of the argument).
 // TWO: a second key set (p.K2 / V2 / km2 / kv_len2 / out_scale2) is attended to after the first, with its own softmax; the first
 // result waits in registers and one sum is stored (IPAdapter processor: text tokens + image tokens, attention_processor.py:233, 268-283).
-template <int D, int BKV, int QT, int OFS, bool ALIGNED, int VAR, int NM = 0, bool TWO = false>
+template <int D, int BKV, int QT, int OFS, bool ALIGNED, bool TWO = false>
 __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) {
   constexpr int NU = BKV / 32;             // 32-key sub-tiles per KV tile
   constexpr int VROW = BKV + 8;            // V^T image row stride (elements): odd number of 16-B slots
@@ -118,16 +112,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
     }
   }
 
-#ifdef A3D_STORAGE_F16
-  constexpr bool TRY_NOMAX = false;
-#else
-  constexpr bool TRY_NOMAX = NM != 0;
-#endif
-  static_assert(NM == 0 || (OFS != OFS_FMA && ALIGNED && ONES), "the max-free pass needs the offset inside the matrix pipe and MFMA row sums");
-  // One complete pass over the keys; returns false when the max-free result must be discarded.
+  // One complete pass over the keys of one key set.
   f32x16_t osave[TWO ? QT : 1][TWO ? MT : 1];      // normalised result of the first key set
-  auto pass = [&](auto nm_c, auto set_c) __attribute__((always_inline)) -> bool {
-  constexpr bool NOMAX = decltype(nm_c)::value;
+  auto pass = [&](auto set_c) __attribute__((always_inline)) {
   constexpr bool SET1 = decltype(set_c)::value;       // this pass reads the second key set
   const uint16_t* const Kp = SET1 ? p.K2 : p.K;
   const uint16_t* const Vp = SET1 ? p.V2 : p.V;
@@ -253,10 +240,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
   const int krow_off = kperm(l31) * KROW + 8 * g;
   const int vrow_off = l31 * VROW + 8 * g;
 
-  // first_c: 2 = the wave-uniform `first` flag decides (exact pass), 1 = this is the first tile, 0 = it is not (max-free pass)
-  auto compute = [&](int buf, int kv0, auto tail_c, auto first_c) {
+  auto compute = [&](int buf, int kv0, auto tail_c) {
     constexpr bool TAIL = decltype(tail_c)::value;
-    constexpr int FM = decltype(first_c)::value;
     const uint16_t* const Ks = Ks0 + buf * KS_ELEMS + krow_off;
     const uint16_t* const Vt = Vt0 + buf * VT_ELEMS + vrow_off;
     // ---- S'^T = K · Q'^T (- offset) for the NU 32-key sub-tiles; one K fragment feeds all QT query sub-tiles
@@ -274,10 +259,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const u32x4_t kf = *reinterpret_cast<const u32x4_t*>(Ks + 32 * u * KROW + 16 * ks);
-        if constexpr ((VAR & 1) != 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int qs = 0; qs < QT; ++qs) sacc[qs][u] = mfma32(kf, qf[qs][ks], sacc[qs][u]);
-        if constexpr ((VAR & 1) != 0) __builtin_amdgcn_s_setprio(0);
       }
     }
     if constexpr (TAIL) {      // keys past kv_len
@@ -351,9 +334,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
         for (int r = 0; r < 16; ++r) sacc[0][u][r] = fmaf(sacc[0][u][r], p.scale_log2, mneg);
     } else {
       // ---- lazy offset update: the common path is max + compare + one wave vote per query sub-tile; the slow
-      //      path re-bases S', rescales O and moves the offset.  Max-free pass: only the first tile sets an offset.
-      if constexpr (FM != 0) {
-      const bool isfirst = (FM == 1) ? true : first;
+      //      path re-bases S', rescales O and moves the offset.
 #pragma unroll
       for (int qs = 0; qs < QT; ++qs) {
         float mx = sacc[qs][0][0];
@@ -361,9 +342,11 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
         for (int u = 0; u < NU; ++u)
 #pragma unroll
           for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[qs][u][r]);
-        if (__any(isfirst || mx > LAZY_THR)) {
+        if (__any(first || mx > LAZY_THR)) {
           const float mxp = fmaxf(mx, __shfl_xor(mx, 32));
-          float delta = isfirst ? mxp + (NOMAX ? 40.f : 0.f) : fmaxf(mxp, 0.f);
+          // (+ 0.f is the v_add_f32 these kernels have always carried here; it changes no result — m_off is +0 when first — and goes
+          // with a change that measures, not with one that promises identical instructions: profiles/attn_dead_variants_asm_diff.md)
+          float delta = first ? mxp + 0.f : fmaxf(mxp, 0.f);
           float new_off = m_off[qs] + delta;
           if constexpr (OFS == OFS_PAD) { new_off = round16(new_off); delta = new_off - m_off[qs]; }
           m_off[qs] = new_off;
@@ -371,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
           for (int u = 0; u < NU; ++u)
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[qs][u][r] -= delta;
-          if (!isfirst) {
+          if (!first) {
             const float alpha = __builtin_amdgcn_exp2f(-delta);
             if constexpr (!ONES) l_run *= alpha;
 #pragma unroll
@@ -387,20 +370,12 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
           }
         }
       }
-      }
       first = false;
     }
 
     // ---- P = exp2(S'), O^T += V^T · P^T   (row D of V^T is all ones: O^T[D] accumulates the row sums)
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
-      u32x4_t vfr[(VAR & 2) ? MT : 1][2];
-      if constexpr ((VAR & 2) != 0) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) vfr[mt][h] = *reinterpret_cast<const u32x4_t*>(Vt + 32 * mt * VROW + 32 * u + 16 * h);
-      }
       u32x4_t pf[QT][2];
 #pragma unroll
       for (int qs = 0; qs < QT; ++qs) {
@@ -415,26 +390,14 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
 #pragma unroll
           for (int j = 0; j < 4; ++j) pf[qs][h][j] = pack16(pv[8 * h + 2 * j], pv[8 * h + 2 * j + 1]);
       }
-      if constexpr ((VAR & 1) != 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          u32x4_t vf;
-          if constexpr ((VAR & 2) != 0) vf = vfr[mt][h];
-          else vf = *reinterpret_cast<const u32x4_t*>(Vt + 32 * mt * VROW + 32 * u + 16 * h);
+          const u32x4_t vf = *reinterpret_cast<const u32x4_t*>(Vt + 32 * mt * VROW + 32 * u + 16 * h);
 #pragma unroll
           for (int qs = 0; qs < QT; ++qs) oacc[qs][mt] = mfma32(vf, pf[qs][h], oacc[qs][mt]);
         }
-      if constexpr ((VAR & 1) != 0) __builtin_amdgcn_s_setprio(0);
-    }
-    if constexpr ((VAR & 4) != 0) {
-#pragma unroll
-      for (int i = 0; i < NU * MT * 2 * QT; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x400, 4, 0);   // 4 TRANS (v_exp)
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // 2 VALU (v_cvt_pk)
-      }
     }
   };
 
@@ -450,35 +413,26 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
   if (ntiles > 1) load_tile(1);
   __syncthreads();
   const int nfast = has_tail ? ntiles - 1 : ntiles;     // tiles the incremental-pointer path may load
-  constexpr std::integral_constant<int, NOMAX ? 0 : 2> FM_LOOP{};
   int t = 0;
   if constexpr (ALIGNED) {
-    if constexpr (NOMAX) {                               // peeled first tile (the launcher guarantees >= 3 tiles, no tail)
-      store_kv(1);
-      load_kv(std::false_type{});
-      compute(0, 0, std::false_type{}, std::integral_constant<int, 1>{});
-      __syncthreads();
-      t = 1;
-    }
     for (; t + 2 < nfast; ++t) {                         // steady state: no clamp, no mask, no div/mod
       store_kv((t + 1) & 1);                             // registers hold tile t+1 (requested one iteration ago)
       load_kv(std::false_type{});                        // tile t+2
-      compute(t & 1, t * BKV, std::false_type{}, FM_LOOP);
+      compute(t & 1, t * BKV, std::false_type{});
       __syncthreads();
     }
   }
   for (; t < ntiles - 1; ++t) {                          // generic / last iterations
     store_kv((t + 1) & 1);
     if (t + 2 < ntiles) load_tile(t + 2);
-    compute(t & 1, t * BKV, std::false_type{}, FM_LOOP);
+    compute(t & 1, t * BKV, std::false_type{});
     __syncthreads();
   }
-  if (has_tail) compute((ntiles - 1) & 1, (ntiles - 1) * BKV, std::true_type{}, FM_LOOP);
-  else compute((ntiles - 1) & 1, (ntiles - 1) * BKV, std::false_type{}, FM_LOOP);
+  if (has_tail) compute((ntiles - 1) & 1, (ntiles - 1) * BKV, std::true_type{});
+  else compute((ntiles - 1) & 1, (ntiles - 1) * BKV, std::false_type{});
 
   // ---- finalize: lane holds O[q = l31][d = 32*mt + 8*qd + 4*g + j] for each query sub-tile
   float inv[QT], l_fin[QT];
-  bool bad = false;
 #pragma unroll
   for (int qs = 0; qs < QT; ++qs) {
     float l_tot;
@@ -489,12 +443,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
     } else {
       l_tot = l_run + __shfl_xor(l_run, 32);
     }
-    bad = bad || !(l_tot < 1.2676506e30f) || !(l_tot > 0.f);
     inv[qs] = oscale / l_tot;
     l_fin[qs] = l_tot;
-  }
-  if constexpr (NOMAX) {
-    if (__syncthreads_or(bad ? 1 : 0)) return false;       // (every wave is also done with the LDS images)
   }
   if constexpr (!TWO) {
     if (p.lse != nullptr) {      // training: log2 of the softmax denominator (m_off: raw-score maximum in the fma form, else the log2-domain offset)
@@ -513,7 +463,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) osave[qs][mt][r] = oacc[qs][mt][r] * inv[qs];
-      return true;
+      return;
     }
   }
 #pragma unroll
@@ -544,18 +494,13 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(const AttnParams p) 
         }
     }
   }
-  return true;
   };    // pass
 
-  if constexpr (TRY_NOMAX) {
-    if (!pass(std::true_type{}, std::false_type{})) pass(std::false_type{}, std::false_type{});
-  } else {
-    pass(std::false_type{}, std::false_type{});
-  }
+  pass(std::false_type{});
   if constexpr (TWO) {
     if (p.K2 != nullptr) {
       __syncthreads();                                     // the LDS images are re-used
-      pass(std::false_type{}, std::true_type{});
+      pass(std::true_type{});
     }
   }
 }
@@ -565,20 +510,20 @@ bool map_ok(const a3d_rowmap* m, int head_dim) {
 }
 
 
-template <int D, int BKV, int QT, int OFS, int VAR = 0, int NM = 0>
+template <int D, int BKV, int QT, int OFS>
 void launch(bool aligned, int groups, hipStream_t s, const AttnParams& p) {
   const int q_tiles = (p.q_len + 128 * QT - 1) / (128 * QT);
   const dim3 grid((unsigned)(p.heads * q_tiles), (unsigned)groups);
-  if (aligned) flash_attn_kernel<D, BKV, QT, OFS, true, VAR, NM><<<grid, dim3(256), 0, s>>>(p);
-  else flash_attn_kernel<D, BKV, QT, OFS, false, 0><<<grid, dim3(256), 0, s>>>(p);
+  if (aligned) flash_attn_kernel<D, BKV, QT, OFS, true><<<grid, dim3(256), 0, s>>>(p);
+  else flash_attn_kernel<D, BKV, QT, OFS, false><<<grid, dim3(256), 0, s>>>(p);
 }
 
 template <int D, int BKV, int OFS>
 void launch_two(bool aligned, int groups, hipStream_t s, const AttnParams& p) {
   const int q_tiles = (p.q_len + 127) / 128;
   const dim3 grid((unsigned)(p.heads * q_tiles), (unsigned)groups);
-  if (aligned) flash_attn_kernel<D, BKV, 1, OFS, true, 0, 0, true><<<grid, dim3(256), 0, s>>>(p);
-  else flash_attn_kernel<D, BKV, 1, OFS, false, 0, 0, true><<<grid, dim3(256), 0, s>>>(p);
+  if (aligned) flash_attn_kernel<D, BKV, 1, OFS, true, true><<<grid, dim3(256), 0, s>>>(p);
+  else flash_attn_kernel<D, BKV, 1, OFS, false, true><<<grid, dim3(256), 0, s>>>(p);
 }
 
 }  // namespace
@@ -637,7 +582,7 @@ static int flash_attn_impl(a3d_stream_t stream, const void* Q, const void* K, co
         if (int rc = A3D_FN(a3d_launch_flash_dm)(exact ? 4 : 5, groups, s, p)) return rc;
         break;
       }
-      launch<40, 64, 2, OFS_PAD, 0>(aligned, groups, s, p);
+      launch<40, 64, 2, OFS_PAD>(aligned, groups, s, p);
       break;
     case 80:
       // LDS-DMA staged kernel (flash_attn_dm80.hip): the default from 512 keys (both storage types).  Otherwise: long sequences take

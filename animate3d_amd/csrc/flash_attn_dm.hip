@@ -10,12 +10,18 @@
 //    exactly two per tile (one full, one with 16 lanes), so the hand-counted wait before the per-tile barrier is vmcnt(2).
 //    Tiles are requested three ahead into a ring of 8 buffers; LDS reads stay in flight across the barrier.
 //  * Dense LDS images (80-byte rows, nothing padded, nothing initialised per tile).  K rows are read with 16-byte reads:
-//    5 r mod 16 is a bijection, so any 16 rows that differ mod 16 are conflict-free.  V rows are stored in a 4x4-transposed
-//    order inside every 16-key group (the DMA source address does the permutation) so that the four keys one
-//    ds_read_b64_tr_b16 group touches lie 4 rows = 80 dwords = 16 banks apart.  The constant parts of the operands — the
-//    1.0 in contraction slot 40 of K that carries the softmax offset, the ones "dimension" 40 of V that produces the row
-//    sums, the zero padding up to 48 / 64 — are not part of the images: the lanes that would read them point at a small
-//    constant region instead (all lanes of a read that share an address are one broadcast).
+//    5 r mod 16 is a bijection, so any 16 rows that differ mod 16 are conflict-free.  V rows are stored in a permuted order
+//    inside every 32-key sub-tile (the DMA source address does the permutation, slot_src) so that the eight keys a 32-lane half
+//    of one ds_read_b64_tr_b16 touches land on eight rows of one parity: 8-dword windows on all 64 banks.  The constant parts
+//    of the operands — the 1.0 in contraction slot 40 of K that carries the softmax offset, the ones "dimension" 40 of V that
+//    produces the row sums, the zero padding up to 48 — are not part of the images: the lanes that would read them point at a
+//    small constant region instead (all lanes of a read that share an address are one broadcast).
+//  * 8 waves x 64 queries (two 32-query sub-tiles per wave, two waves per SIMD, up to 256 registers): every K / V fragment read
+//    from LDS feeds two MFMAs, and one staged copy of K/V serves 512 queries.
+//  * O^T += V^T·P^T through v_mfma_f32_16x16x32: O^T has 41 useful rows (40 dims + the ones row), i.e. 48 in 16-row tiles where
+//    32-row tiles need 64: 24 instead of 28 MFMA-equivalents per 64 x 64 tile.  The 32x32 score tile keeps a query in lane & 31,
+//    the 16x16x32 B operand wants it in lane & 15: one v_permlane16_swap per packed pair of P moves the odd 16-lane rows of the
+//    first key half against the even rows of the second (16 per 64 x 64 tile).
 //  * NO running row maximum.  P = exp2(S - m) is stored in 16 bits and accumulated in fp32; the result does not depend on m as long
 //    as nothing overflows or vanishes.  m is fixed per query before the key loop (maximum of 32 sample scores + DM_BIAS, carried in
 //    contraction slot 40 of Q) and nothing is checked inside the loop; at the end the row sum that the matrix pipe produces anyway
@@ -58,22 +64,15 @@ extern __shared__ __attribute__((aligned(16))) uint8_t dm_smem[];
 A3D_DEV u32x4_t dm_lds128(uint32_t off) { return *reinterpret_cast<const u32x4_t*>(dm_smem + off); }
 A3D_DEV u32x2_t dm_ldstr(uint32_t off) { return lds_tr16_b64(reinterpret_cast<const uint16_t*>(dm_smem + off)); }
 
-// FLAGS: 1 = max-free softmax with exact re-run (bf16 storage only), 2 = static s_setprio(1) for the second-dispatched half
-//        of the workgroup (MI355X_MICROARCH.md "static priority for the younger half"), 4 = O^T += V^T·P^T through
-//        v_mfma_f32_16x16x32: O^T has 41 useful rows (40 dims + the ones row), i.e. 48 in 16-row tiles instead of 64 in
-//        32-row tiles: 24 instead of 28 MFMA-equivalents per 64 x 64 tile.  The 32x32 score tile keeps a query in lane & 31,
-//        the 16x16x32 B operand wants it in lane & 15: one v_permlane16_swap per packed pair of P moves the odd 16-lane rows
-//        of the first key half against the even rows of the second (16 per 64 x 64 tile).
-// QT: query sub-tiles of 32 per wave.  2 = 8 waves x 64 queries (two waves per SIMD, up to 256 registers); 1 = 16 waves x 32 queries
-//     (four waves per SIMD, 128 registers: twice the LDS fragment reads per MFMA, but four instruction streams per SIMD to
-//     overlap matrix and vector work and to hide LDS latency and barrier skew).  Both stage one copy of K/V for 512 queries.
+// FLAGS: 5 = max-free first pass with exact re-run on overflow, 4 = exact pass only.  QT: 32-query sub-tiles per wave, always 2.
+// (the template arguments are part of the kernel's name, by which profiles and the benchmark's roofline entry find it: they stay as they are)
 template <int FLAGS, int QT>
-__global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const AttnParams p) {
-  constexpr int D = 40, KS = 3, MT = 2, NW = 16 / QT, NT = 64 * NW, BQ = 512;
-  constexpr int NDMA = QT;                                // LDS-DMA instructions per wave and tile (QT = 1: waves 0..9 one each)
+__global__ __launch_bounds__(512, 2) void flash_attn_dm_kernel(const AttnParams p) {
+  static_assert(QT == 2 && (FLAGS & ~1) == 4, "the kernel exists as <4, 2> (exact pass only) and <5, 2> (max-free first pass)");
+  constexpr int D = 40, KS = 3, NW = 8, NT = 64 * NW, BQ = 512;
+  constexpr int NDMA = 2;                                 // LDS-DMA instructions per wave and tile
   constexpr int KS_PAD = 2, G_PAD = 1;                    // fragment slot of contraction index 40
   constexpr int NEXP = 16 * QT, NCVT = 8 * QT;
-  constexpr bool PV16 = (FLAGS & 4) != 0;
   constexpr bool TRY_NOMAX = (FLAGS & 1) != 0;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
   }
 
   // ---- DMA lanes.  Chunk slot s of a tile buffer (16 B at byte 16 s): s < 320 is K row s / 5, piece s % 5; s >= 320 is V
-  // physical row (s - 320) / 5, which holds key 16 (r / 16) + 4 (r & 3) + ((r >> 2) & 3).  Wave w issues slots 64 w .. + 63
+  // physical row r = (s - 320) / 5, which holds the key slot_src works out.  Wave w issues slots 64 w .. + 63
   // (instruction A: K for w < 5, V otherwise) and 512 + 16 w .. + 15 (instruction B, 16 lanes: V).
   const int64_t ld = p.km.ld;
   const int64_t kgbase = map_group_base(p.km, grp);
@@ -125,19 +124,16 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
     const int s2 = isk ? slot : slot - 320;
     const int prow = s2 / 5, c = s2 % 5;
     int key = prow;
-    if (!isk) {
-      if constexpr (PV16) {     // row = 16 half + 8 b4 + 2 j + rr  holds key 16 b4 + 8 half + 4 rr + j of its 32-key sub-tile
-        const int pr = prow & 31;
-        key = (prow & ~31) | (16 * ((pr >> 3) & 1) + 8 * (pr >> 4) + 4 * (pr & 1) + ((pr >> 1) & 3));
-      } else {
-        key = (prow & ~15) | (4 * (prow & 3) + ((prow >> 2) & 3));
-      }
+    if (!isk) {                 // row = 16 half + 8 b4 + 2 j + rr  holds key 16 b4 + 8 half + 4 rr + j of its 32-key sub-tile
+      const int pr = prow & 31;
+      key = (prow & ~31) | (16 * ((pr >> 3) & 1) + 8 * (pr >> 4) + 4 * (pr & 1) + ((pr >> 1) & 3));
     }
     return (uint32_t)(((int64_t)key * ld + c * 8) * 2);
   };
+  // (a tile has 10 full instructions' worth of slots; w < 8 always holds, but the compiler cannot see it, and without the select it
+  // orders the prologue differently: profiles/attn_dead_variants_asm_diff.md)
   const uint32_t voffA = slot_src(w < 10 ? 64 * w + lane : lane);
-  const uint32_t voffB = slot_src(QT == 2 ? 512 + 16 * w + i16 : 0);
-  const uint64_t maskA = w < 10 ? ~0ull : 0ull;
+  const uint32_t voffB = slot_src(512 + 16 * w + i16);
   // sample sub-tile (DM_SAMPLED): slot s = 64 w + lane < 160 is piece s % 5 of sample row s / 5 = key (s / 5) * (kv_len / 32)
   uint32_t voffS = 0;
   if constexpr (DM_SAMPLED) {
@@ -154,22 +150,15 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
   uint32_t kmul = g ? 0u : 1u;
   asm volatile("" : "+v"(kmul));      // opaque: keeps  lane + mul * offset  one v_mad_u32_u24 (the compiler otherwise builds mov + cndmask + add)
   const int c4 = i16 & 3;
-  // 32x32 PV: a 16-lane group (q4) reads keys 8 (q4 >> 1) + 4 rr + (i16 >> 2) of a 16-key half, dims 16 (q4 & 1) + 4 c4 of a 32-row tile;
-  //           rows are stored 4x4-transposed inside every 16-key group.
-  // 16x16 PV: a group reads keys [0, 16, 8, 24][q4] + 4 rr + (i16 >> 2), dims 4 c4 of a 16-row tile; row = 16 (q4 >> 1) + 8 (q4 & 1) + 2 (i16 >> 2) + rr
-  //           (the eight keys of a 32-lane half land on eight rows of one parity: 8-dword windows on all 64 banks).
-  const uint32_t vrow = PV16 ? (uint32_t)((16 * (q4 >> 1) + 8 * (q4 & 1) + 2 * (i16 >> 2)) * DM_ROWB)
-                             : (uint32_t)((4 * (i16 >> 2) + 2 * (q4 >> 1)) * DM_ROWB);
-  const uint32_t vlane0 = PV16 ? vrow + (uint32_t)(8 * c4) : vrow + (uint32_t)(2 * (16 * (q4 & 1) + 4 * c4));      // O^T rows 0..31: all data
-  const bool v1_data = PV16 ? c4 < 2 : ((q4 & 1) == 0 && c4 < 2);               // O^T rows 32..: dims 32..39 | ones | zeros
-  const bool v1_one = PV16 ? c4 == 2 : ((q4 & 1) == 0 && c4 == 2);
+  // V^T fragments: a 16-lane group (q4) reads keys [0, 16, 8, 24][q4] + 4 rr + (i16 >> 2), dims 4 c4 of a 16-row tile; row = 16 (q4 >> 1) + 8 (q4 & 1) + 2 (i16 >> 2) + rr
+  // (the eight keys of a 32-lane half land on eight rows of one parity: 8-dword windows on all 64 banks).
+  const uint32_t vrow = (uint32_t)((16 * (q4 >> 1) + 8 * (q4 & 1) + 2 * (i16 >> 2)) * DM_ROWB);
+  const uint32_t vlane0 = vrow + (uint32_t)(8 * c4);                            // O^T rows 0..31: all data
+  const bool v1_data = c4 < 2;                                                  // O^T rows 32..47: dims 32..39 | ones | zeros
+  const bool v1_one = c4 == 2;
   const uint32_t vlane1 = v1_data ? vrow + (uint32_t)(2 * (32 + 4 * c4)) : (v1_one ? (uint32_t)DM_CV : (uint32_t)(DM_CV + 8));
   uint32_t vmul = v1_data ? 1u : 0u;
   asm volatile("" : "+v"(vmul));
-
-  if constexpr ((FLAGS & 2) != 0) {
-    if (w >= 4) __builtin_amdgcn_s_setprio(1);
-  }
 
   // ---- pieces shared by the two passes
   const uint16_t* gA = nullptr;
@@ -187,61 +176,38 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
     gA += stp; gB += stp;
   };
   auto dma_a = [&](int tile) __attribute__((always_inline)) {
-    if constexpr (QT == 2) {
-      dm_glds16(voffA, gA, lds0 + (uint32_t)((tile & (DM_RING - 1)) * DM_TILEB + 1024 * w));
-    } else {
-      dm_glds16_m(voffA, gA, lds0 + (uint32_t)((tile & (DM_RING - 1)) * DM_TILEB + 1024 * (w < 10 ? w : 0)), maskA);
-      dma_advance();
-    }
+    dm_glds16(voffA, gA, lds0 + (uint32_t)((tile & (DM_RING - 1)) * DM_TILEB + 1024 * w));
   };
-  auto dma_b = [&](int tile) __attribute__((always_inline)) {      // second instruction of a tile (QT = 2); then the bases move on
-    if constexpr (QT == 2) {
-      dm_glds16_q(voffB, gB, lds0 + (uint32_t)((tile & (DM_RING - 1)) * DM_TILEB + 8192 + 256 * w));
-      dma_advance();
-    }
+  auto dma_b = [&](int tile) __attribute__((always_inline)) {      // second instruction of a tile; then the bases move on
+    dm_glds16_q(voffB, gB, lds0 + (uint32_t)((tile & (DM_RING - 1)) * DM_TILEB + 8192 + 256 * w));
+    dma_advance();
   };
-  f32x16_t oacc[QT][MT];       // 32x32 PV: O^T tiles [query sub-tile][32 rows]
-  f32x4_t oacc16[3][2 * QT];   // 16x16 PV: O^T tiles [16 rows][16 queries]; rows 4 q4 + r, query 16 nb + i16
+  f32x4_t oacc16[3][2 * QT];   // O^T tiles [16 rows][16 queries]; rows 4 q4 + r, query 16 nb + i16
   u32x4_t kf[KS];
-  u32x4_t vf[MT][2];           // V^T fragments of the sub-tile whose P is multiplied next (32x32 PV: [row tile][key half])
-  u32x4_t vf16[3];             // (16x16 PV: [row tile], 32 keys each)
+  u32x4_t vf16[3];             // V^T fragments of the sub-tile whose P is multiplied next: [row tile], 32 keys each
   auto read_k = [&](uint32_t koff) __attribute__((always_inline)) {          // K fragments of the sub-tile at byte offset koff
     const uint32_t a = klane + koff, a2 = __umul24(kmul, koff) + klane2;
     kf[0] = dm_lds128(a); kf[1] = dm_lds128(a + 32); kf[2] = dm_lds128(a2);
   };
   // V^T fragment half i of the sub-tile at a0 / a1 (a1: the row tile that holds the constants)
   auto read_vhalf = [&](auto i_c, uint32_t a0, uint32_t a1) __attribute__((always_inline)) {
-    constexpr int i = decltype(i_c)::value;
-    if constexpr (PV16) {
-      constexpr int mb = i / 2, rr = i % 2;
-      const u32x2_t t = dm_ldstr((mb == 2 ? a1 : a0 + 32 * mb) + rr * DM_ROWB);
-      vf16[mb][2 * rr] = t[0];
-      vf16[mb][2 * rr + 1] = t[1];
-    } else {
-      constexpr int mt = i / 4, h = (i / 2) % 2, rr = i % 2;
-      const u32x2_t t = dm_ldstr((mt ? a1 : a0) + (16 * h + rr) * DM_ROWB);
-      vf[mt][h][2 * rr] = t[0];
-      vf[mt][h][2 * rr + 1] = t[1];
-    }
+    constexpr int i = decltype(i_c)::value, mb = i / 2, rr = i % 2;
+    const u32x2_t t = dm_ldstr((mb == 2 ? a1 : a0 + 32 * mb) + rr * DM_ROWB);
+    vf16[mb][2 * rr] = t[0];
+    vf16[mb][2 * rr + 1] = t[1];
   };
-  constexpr int NVH = PV16 ? 6 : 8;          // fragment halves per sub-tile
+  constexpr int NVH = 6;                     // fragment halves per sub-tile
   auto read_v = [&](uint32_t voff) __attribute__((always_inline)) {
     const uint32_t a0 = vlane0 + voff, a1 = __umul24(vmul, voff) + vlane1;
     static_for<NVH>([&](auto i_c) __attribute__((always_inline)) { read_vhalf(i_c, a0, a1); });
   };
-  // PV MFMA instruction i of a sub-tile (32x32: 8 instructions of 32 cycles; 16x16: 12 of 16 cycles); P as packed by finish_p
-  constexpr int NPVI = PV16 ? 6 * QT : 4 * QT;
+  // PV MFMA instruction i of a sub-tile (12 of 16 cycles); P as swap_p leaves it
+  constexpr int NPVI = 6 * QT;
   auto pv_mfma = [&](auto i_c, u32x4_t (&P)[QT][2]) __attribute__((always_inline)) {
-    constexpr int i = decltype(i_c)::value;
-    if constexpr (PV16) {
-      constexpr int mb = i / (2 * QT), nb = i % (2 * QT);
-      oacc16[mb][nb] = mfma16(vf16[mb], P[nb / 2][nb % 2], oacc16[mb][nb]);
-    } else {
-      constexpr int mt = i / (2 * QT), h = (i / QT) % 2, qs = i % QT;
-      oacc[qs][mt] = mfma32(vf[mt][h], P[qs][h], oacc[qs][mt]);
-    }
+    constexpr int i = decltype(i_c)::value, mb = i / (2 * QT), nb = i % (2 * QT);
+    oacc16[mb][nb] = mfma16(vf16[mb], P[nb / 2][nb % 2], oacc16[mb][nb]);
   };
-  // 16x16 PV: turn the packed probabilities of query sub-tile qs, pair jj (P[qs][h][jj] = keys 16 h + 8 g + 2 jj, + 1 of query l31) into the
+  // turn the packed probabilities of query sub-tile qs, pair jj (P[qs][h][jj] = keys 16 h + 8 g + 2 jj, + 1 of query l31) into the
   // B operands of query blocks 2 qs (in P[qs][0]) and 2 qs + 1 (in P[qs][1]): 16-lane row q4 then holds keys [0, 16, 8, 24][q4] + 2 jj, + 1
   auto swap_p = [&](auto k_c, u32x4_t (&P)[QT][2]) __attribute__((always_inline)) {
     constexpr int k = decltype(k_c)::value, qs = k / 4, jj = k % 4;
@@ -251,13 +217,8 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
   };
   auto clear_o = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int qs = 0; qs < QT; ++qs) {
+    for (int qs = 0; qs < QT; ++qs)
       if (g == G_PAD) qf[qs][KS_PAD][0] = 0u;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[qs][mt][r] = 0.f;
-    }
 #pragma unroll
     for (int mb = 0; mb < 3; ++mb)
 #pragma unroll
@@ -310,57 +271,44 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
     }
     return wide;
   };
-  // row sums (O^T row 40): 32x32 layout: register 4 of the second row tile, half 0 (query l31); 16x16 layout: register 0 of row
-  // tile 2 in lanes 32..47 (query i16 of block nb).  Returns 1 / sum scaled for the store; `bad` = sum unusable (max-free pass).
-  constexpr int NINV = PV16 ? 2 * QT : QT;
+  // row sums (O^T row 40): register 0 of row tile 2 in lanes 32..47 (query i16 of block nb).  Returns 1 / sum scaled for the
+  // store; `bad` = sum unusable (max-free pass).
+  constexpr int NINV = 2 * QT;
   float l_row[NINV];
   auto row_sums = [&](float (&inv)[NINV]) __attribute__((always_inline)) -> bool {
     bool bad = false;
 #pragma unroll
     for (int i = 0; i < NINV; ++i) {
-      float l_tot;
-      if constexpr (PV16) l_tot = __shfl(oacc16[2][i][0], 32 + i16);
-      else l_tot = __shfl(oacc[i][1][4], l31);
+      const float l_tot = __shfl(oacc16[2][i][0], 32 + i16);
       bad = bad || !(l_tot < DM_L_BAD) || !(l_tot > 0.f);
       inv[i] = p.out_scale / l_tot;
       l_row[i] = l_tot;
     }
     return bad;
   };
-  // training: log2 of the softmax denominator per query = offset + log2(row sum); the offset of query l31 of sub-tile qs is what the
+  // training: log2 of the softmax denominator per query = offset + log2(row sum); the offset of query ql of sub-tile qs is what the
   // lanes of half G_PAD carry (negated, 16 bits) in contraction slot 40 of their Q fragment
   auto store_lse = [&]() __attribute__((always_inline)) {
     if (p.lse == nullptr) return;
 #pragma unroll
     for (int i = 0; i < NINV; ++i) {
-      const int qs = PV16 ? i / 2 : i, ql = PV16 ? 16 * (i % 2) + i16 : l31;
+      const int qs = i / 2, ql = 16 * (i % 2) + i16;
       const float noff = lo16((uint32_t)__shfl((int)qf[qs][KS_PAD][0], 32 * G_PAD + ql));
       const int q_idx = qt * BQ + wid * 32 * QT + 32 * qs + ql;
-      if (q_idx < p.q_len && (PV16 ? q4 == 0 : g == 0))
+      if (q_idx < p.q_len && q4 == 0)
         p.lse[((int64_t)grp * p.heads + head) * p.q_len + q_idx] = __builtin_amdgcn_logf(l_row[i]) - noff;
     }
   };
-  auto store_out = [&](const float (&inv)[NINV]) __attribute__((always_inline)) {
-    if constexpr (PV16) {      // lane holds O[q = 16 nb + i16][d = 16 mb + 4 q4 + r]
+  auto store_out = [&](const float (&inv)[NINV]) __attribute__((always_inline)) {      // lane holds O[q = 16 nb + i16][d = 16 mb + 4 q4 + r]
 #pragma unroll
-      for (int nb = 0; nb < 2 * QT; ++nb) {
-        const int q_idx = qt * BQ + wid * 32 * QT + 16 * nb + i16;
-        if (q_idx < p.q_len) {
-          uint16_t* orow = p.O + map_row(p.om, grp, q_idx) * p.om.ld + hoff;
+    for (int nb = 0; nb < 2 * QT; ++nb) {
+      const int q_idx = qt * BQ + wid * 32 * QT + 16 * nb + i16;
+      if (q_idx < p.q_len) {
+        uint16_t* orow = p.O + map_row(p.om, grp, q_idx) * p.om.ld + hoff;
 #pragma unroll
-          for (int mb = 0; mb < 3; ++mb) {
-            const int d = 16 * mb + 4 * q4;
-            if (d < D) store4(orow + d, p.accumulate, oacc16[mb][nb][0] * inv[nb], oacc16[mb][nb][1] * inv[nb], oacc16[mb][nb][2] * inv[nb], oacc16[mb][nb][3] * inv[nb]);
-          }
-        }
-      }
-    } else {                   // lane holds O[q = l31][d = 32*mt + 8*qd + 4*g + j] for each query sub-tile
-#pragma unroll
-      for (int qs = 0; qs < QT; ++qs) {
-        const int q_idx = qt * BQ + wid * 32 * QT + qs * 32 + l31;
-        if (q_idx < p.q_len) {
-          uint16_t* orow = p.O + map_row(p.om, grp, q_idx) * p.om.ld + hoff;
-          store_acc8<D, MT>(orow, g, p.accumulate, [&](int mt, int r) __attribute__((always_inline)) { return oacc[qs][mt][r] * inv[qs]; });
+        for (int mb = 0; mb < 3; ++mb) {
+          const int d = 16 * mb + 4 * q4;
+          if (d < D) store4(orow + d, p.accumulate, oacc16[mb][nb][0] * inv[nb], oacc16[mb][nb][1] * inv[nb], oacc16[mb][nb][2] * inv[nb], oacc16[mb][nb][3] * inv[nb]);
         }
       }
     }
@@ -378,15 +326,15 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
 #pragma unroll
       for (int h = 0; h < 2; ++h) { pA[qs][h] = u32x4_t{0u, 0u, 0u, 0u}; pB[qs][h] = u32x4_t{0u, 0u, 0u, 0u}; }
 
-    // One pipeline step j: the matrix pipe does O += V^T(j-1)·P(j-1) (8 MFMAs, fragments vf read during step j-1), then
-    // S(j+1) = K(j+1)·Q^T (6 MFMAs, fragments read in slot 3); the VALU turns S(j) into P(j) over all 14 slots.  With the PV
+    // One pipeline step j: the matrix pipe does O += V^T(j-1)·P(j-1) (12 MFMAs of 16 cycles, fragments vf16 read during step j-1), then
+    // S(j+1) = K(j+1)·Q^T (6 MFMAs of 32 cycles, fragments read in slot 3); the VALU turns S(j) into P(j) over all 12 slots.  With the PV
     // block first, S(j+1) is born when half of S(j) is already dead: 48 instead of 64 score registers (the QK-first order
     // of flash_attn_il_kernel does not fit 256 registers here without spilling, and a spill reload is a vmcnt(0) that drains
     // the DMA queue).  kOff / vOff: LDS byte offsets of K sub-tile j+1 and V sub-tile j.
     auto step = [&](auto do_qk_c, auto do_pv_c, f32x16_t (&sCur)[QT], f32x16_t (&sNext)[QT], u32x4_t (&pCur)[QT][2],
                     u32x4_t (&pPrev)[QT][2], uint32_t kOff, uint32_t vOff, auto&& hook) __attribute__((always_inline)) {
       constexpr bool DO_QK = decltype(do_qk_c)::value, DO_PV = decltype(do_pv_c)::value;
-      constexpr int PPS = PV16 ? 2 : 1;                                   // PV instructions per slot (a slot = 32 matrix-pipe cycles)
+      constexpr int PPS = 2;                                              // PV instructions per slot (a slot = 32 matrix-pipe cycles)
       constexpr int NPV = DO_PV ? NPVI / PPS : 0, NQK = DO_QK ? KS * QT : 0, NS = NPV + NQK;
       constexpr int KSLOT = NPV >= 4 ? 3 : 0, VS0 = NPV + 1;              // K fragments early in the PV block; V halves VPS per slot from VS0
       constexpr int VPS = DO_QK ? (NVH + NQK - 2) / (NQK - 1) : 1;
@@ -431,23 +379,19 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
         });
         constexpr int C0 = cdone(s - 1), C1 = cdone(s);
         static_for<C1 - C0>([&](auto c_c) __attribute__((always_inline)) { do_cvt(std::integral_constant<int, C0 + decltype(c_c)::value>{}); });
-        if constexpr (PV16) {
-          static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) {
-            constexpr int k = decltype(k_c)::value, need = (k / 4) * 8 + 4 + (k % 4);
-            if constexpr (need < cdone(s - 1) && !(need < cdone(s - 2))) swap_p(k_c, pCur);
-          });
-        }
+        static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) {
+          constexpr int k = decltype(k_c)::value, need = (k / 4) * 8 + 4 + (k % 4);
+          if constexpr (need < cdone(s - 1) && !(need < cdone(s - 2))) swap_p(k_c, pCur);
+        });
         __builtin_amdgcn_sched_barrier(0);
       });
       {
         constexpr int C0 = cdone(NS - 1);
         static_for<NCVT - C0>([&](auto c_c) __attribute__((always_inline)) { do_cvt(std::integral_constant<int, C0 + decltype(c_c)::value>{}); });
-        if constexpr (PV16) {
-          static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) {
-            constexpr int k = decltype(k_c)::value, need = (k / 4) * 8 + 4 + (k % 4);
-            if constexpr (!(need < cdone(NS - 2))) swap_p(k_c, pCur);
-          });
-        }
+        static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) {
+          constexpr int k = decltype(k_c)::value, need = (k / 4) * 8 + 4 + (k % 4);
+          if constexpr (!(need < cdone(NS - 2))) swap_p(k_c, pCur);
+        });
       }
     };
 
@@ -492,9 +436,6 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
       if constexpr (!LAST) {
         // tile t+2 (requested one iteration ago) must be complete for everybody; tile t+3's two requests may stay in flight.
         // LDS reads stay in flight too: no buffer is re-used within four iterations.
-#ifdef A3D_ABLATIONS
-        if constexpr ((FLAGS & 16) != 0) { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(NDMA) : "memory"); } else      // timing ablation: no barrier (results may be wrong)
-#endif
         if constexpr (DMA) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "i"(NDMA) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       }
@@ -553,20 +494,13 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
               const float alpha = __builtin_amdgcn_exp2f(-delta);
 #pragma unroll
               for (int r = 0; r < 16; ++r) sc[qs][r] -= delta;
-              if constexpr (PV16) {          // the query of O block 2 qs + a, lane i16 is the score tile's lane 16 a + i16
 #pragma unroll
-                for (int a = 0; a < 2; ++a) {
-                  const float alpha_o = __shfl(alpha, 16 * a + i16);
+              for (int a = 0; a < 2; ++a) {      // the query of O block 2 qs + a, lane i16 is the score tile's lane 16 a + i16
+                const float alpha_o = __shfl(alpha, 16 * a + i16);
 #pragma unroll
-                  for (int mb = 0; mb < 3; ++mb)
+                for (int mb = 0; mb < 3; ++mb)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) oacc16[mb][2 * qs + a][r] *= alpha_o;
-                }
-              } else {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                  for (int r = 0; r < 16; ++r) oacc[qs][mt][r] *= alpha;
+                  for (int r = 0; r < 4; ++r) oacc16[mb][2 * qs + a][r] *= alpha_o;
               }
               if (g == G_PAD) qf[qs][KS_PAD][0] = pack16(-new_off, 0.f);
             }
@@ -580,7 +514,7 @@ __global__ __launch_bounds__(1024 / QT, 4 / QT) void flash_attn_dm_kernel(const 
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
               pf[qs][h][jj] = pack16(__builtin_amdgcn_exp2f(sc[qs][8 * h + 2 * jj]), __builtin_amdgcn_exp2f(sc[qs][8 * h + 2 * jj + 1]));
-        if constexpr (PV16) static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) { swap_p(k_c, pf); });
+        static_for<4 * QT>([&](auto k_c) __attribute__((always_inline)) { swap_p(k_c, pf); });
         read_v(tb + DM_VOFF + sub * DM_UNITB);
         static_for<NPVI>([&](auto i_c) __attribute__((always_inline)) { pv_mfma(i_c, pf); });
       }
@@ -611,15 +545,14 @@ int launch_dm(int groups, hipStream_t s, const AttnParams& p) {
         return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_dm_kernel<FLAGS, QT>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, DM_SMEM_BYTES); })) return rc;
   const int q_tiles = (p.q_len + 511) / 512;
-  flash_attn_dm_kernel<FLAGS, QT><<<dim3((unsigned)(p.heads * q_tiles), (unsigned)groups), dim3(1024 / QT), DM_SMEM_BYTES, s>>>(p);
+  flash_attn_dm_kernel<FLAGS, QT><<<dim3((unsigned)(p.heads * q_tiles), (unsigned)groups), dim3(512), DM_SMEM_BYTES, s>>>(p);
   return a3d_launch_status();
 }
 
 }  // namespace
 
-// flags: 5 = max-free first pass + exact re-run on overflow (the default), 4 = exact pass only; both with P·V through the 16x16x32 MFMA and
-// 8 waves x 64 queries (the other flag sets of flash_attn_dm_kernel were round-3 A/B variants: profiles/README.md).  Shapes: head_dim 40,
-// kv_len % 64 == 0, kv_len >= 256, aligned segments (checked by the caller).
+// flags: 5 = max-free first pass + exact re-run on overflow (the default), 4 = exact pass only.  Shapes: head_dim 40, kv_len % 64 == 0,
+// kv_len >= 256, aligned segments (checked by the caller).
 int A3D_FN(a3d_launch_flash_dm)(int flags, int groups, hipStream_t s, const AttnParams& p) {
   switch (flags) {
     case 4: return launch_dm<4, 2>(groups, s, p);

@@ -115,9 +115,7 @@ A3D_DEV void dm_count(const AttnParams& p, int which) {
   if (p.counters != nullptr && threadIdx.x == 0) atomicAdd(p.counters + which, 1u);
 }
 
-// ---- output epilogue.  The 32x32 O^T accumulator tiles of a wave leave lane (l31, half g) with O[q = l31][d = 32 mt + 8 qd + 4 g + j] in
-// register 4 qd + j of tile mt; `orow` is the lane's row of O at its head, `val(mt, r)` the finished float of register r of tile mt.
-// four consecutive dims: 8 bytes at dst, added to what is there if `accumulate`
+// ---- output epilogue: four consecutive dims, 8 bytes at dst, added to what is there if `accumulate`
 A3D_DEV void store4(uint16_t* dst, bool accumulate, float v0, float v1, float v2, float v3) {
   if (accumulate) {
     const u32x2_t prev = *reinterpret_cast<const u32x2_t*>(dst);
@@ -127,17 +125,6 @@ A3D_DEV void store4(uint16_t* dst, bool accumulate, float v0, float v1, float v2
   o[0] = pack16(v0, v1);
   o[1] = pack16(v2, v3);
   *reinterpret_cast<u32x2_t*>(dst) = o;
-}
-// 8 bytes per access, in the accumulators' own layout
-template <int D, int MT, typename F>
-A3D_DEV void store_acc8(uint16_t* orow, int g, bool accumulate, F&& val) {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int d = 32 * mt + 8 * qd + 4 * g;
-      if (d < D) store4(orow + d, accumulate, val(mt, 4 * qd), val(mt, 4 * qd + 1), val(mt, 4 * qd + 2), val(mt, 4 * qd + 3));
-    }
 }
 A3D_DEV uint32_t fa_lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
