@@ -50,7 +50,7 @@ from __future__ import annotations
 
 import ctypes
 import itertools
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -145,7 +145,7 @@ def _aligned16(t: torch.Tensor) -> torch.Tensor:
 
 class _DeformGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scaling, rotation, xyz, timestamps, image_to_time, grid_size, flags, plan, net_names, *params):
+    def forward(ctx, scaling, rotation, xyz, timestamps, image_to_time, image_plan, grid_size, flags, plan, net_names, *params):
         ctx.set_materialize_grads(False)                         # an output outside the loss arrives in backward as None, not as zeros
         lib, dev = load_library(), xyz.device
         N, T = xyz.shape[0], timestamps.shape[0]
@@ -156,9 +156,12 @@ class _DeformGaussians(torch.autograd.Function):
         w = _pack_weights(nets, dev)
         i2t = torch.arange(T, device=dev) if image_to_time is None else image_to_time.to(dev).long()
         B = i2t.shape[0]
-        img_list = torch.argsort(i2t, stable=True).to(torch.int32)
-        img_start = torch.zeros(T + 1, dtype=torch.int32, device=dev)
-        img_start[1:] = torch.cumsum(torch.bincount(i2t, minlength=T), 0)
+        if image_plan is not None:                               # counted on the host by the caller: nothing is read back here
+            img_list, img_start = image_plan
+        else:
+            img_list = torch.argsort(i2t, stable=True).to(torch.int32)
+            img_start = torch.zeros(T + 1, dtype=torch.int32, device=dev)
+            img_start[1:] = torch.cumsum(torch.bincount(i2t, minlength=T), 0)
         x, sc, ts = xyz.detach().contiguous(), scaling.detach().contiguous(), timestamps.detach().contiguous()
         ro = _aligned16(rotation.detach().contiguous())
         f32 = dict(dtype=torch.float32, device=dev)
@@ -201,14 +204,19 @@ class _DeformGaussians(torch.autograd.Function):
                 continue
             grads.append(d_w[slot[name], :1024].view(32, 32).clone())
             grads.append(d_w[slot[name], 1024:1024 + k * 32].view(k, 32).clone())
-        return (d_scaling, d_rotation, None, None, None, None, None, None, None, *grads)
+        return (d_scaling, d_rotation, None, None, None, None, None, None, None, None, *grads)
 
 
 def deform_gaussians(xyz: torch.Tensor, scaling: torch.Tensor, rotation: torch.Tensor, timestamps: torch.Tensor, grids, networks, *,
                      image_to_time: Optional[torch.Tensor] = None, use_global_trans: bool = False, deform_scales: bool = True,
-                     first_frame_trainable: bool = False, plan: Optional[BinningPlan] = None):
+                     first_frame_trainable: bool = False, plan: Optional[BinningPlan] = None,
+                     image_plan: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """``grids``: two sequences of six planes; ``networks``: {name: (layers.0.weight, layers.2.weight)} with the three ``delta_*`` networks
-    and, for ``use_global_trans``, the two ``global_*`` ones.  Returns (means [B, N, 3], scales [B, N, 3], rotations [B, N, 4])."""
+    and, for ``use_global_trans``, the two ``global_*`` ones.  Returns (means [B, N, 3], scales [B, N, 3], rotations [B, N, 4]).
+
+    ``image_plan``: ``(img_list [B] int32, img_start [T + 1] int32)``, the images stable-sorted by frame and the first sorted position of
+    every frame, for a caller that knows ``image_to_time`` on the host (``cameras.CameraBatch.image_plan``) and vouches for it.  Without
+    it the two are counted from ``image_to_time`` on the device, which range-checks it and synchronises with the host."""
     for name, t in (("xyz", xyz), ("scaling", scaling), ("rotation", rotation), ("timestamps", timestamps)):
         require_f32_cuda(name, t)
     if xyz.requires_grad:
@@ -241,10 +249,16 @@ def deform_gaussians(xyz: torch.Tensor, scaling: torch.Tensor, rotation: torch.T
     if image_to_time is not None:
         if image_to_time.dim() != 1 or image_to_time.dtype not in (torch.int64, torch.int32):
             raise ValueError("image_to_time: a 1-D integer tensor of indices into timestamps")
+    if image_plan is not None:
+        B = timestamps.shape[0] if image_to_time is None else image_to_time.shape[0]
+        img_list, img_start = image_plan
+        for name, t, n in (("img_list", img_list, B), ("img_start", img_start, timestamps.shape[0] + 1)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (n,) and t.is_contiguous()):
+                raise ValueError(f"image_plan: {name} must be a contiguous int32 CUDA tensor of shape [{n}]")
     if plan is None or not plan.matches(xyz, grid_size):
         plan = BinningPlan(xyz, grid_size)
     flags = (1 if use_global_trans else 0) | (2 if deform_scales else 0) | (4 if first_frame_trainable else 0)
-    return _DeformGaussians.apply(scaling, rotation, xyz, timestamps, image_to_time, grid_size, flags, plan, names, *flat, *weights)
+    return _DeformGaussians.apply(scaling, rotation, xyz, timestamps, image_to_time, image_plan, grid_size, flags, plan, names, *flat, *weights)
 
 
 class _MLP(nn.Module):
@@ -291,7 +305,8 @@ class HexPlaneDeformation(nn.Module):
             self._plan = BinningPlan(xyz, self.grid_size)
         return self._plan
 
-    def forward(self, xyz, scaling, rotation, timestamps, image_to_time=None, deform_scales: bool = True, first_frame_trainable: bool = False):
+    def forward(self, xyz, scaling, rotation, timestamps, image_to_time=None, deform_scales: bool = True, first_frame_trainable: bool = False,
+                image_plan=None):
         require_f32_cuda("xyz", xyz)
         if xyz.requires_grad:
             raise NotImplementedError("xyz.requires_grad: the 4-D stage keeps the positions fixed")
@@ -299,4 +314,4 @@ class HexPlaneDeformation(nn.Module):
         nets = {name: getattr(self, name).weights() for name in names}
         return deform_gaussians(xyz, scaling, rotation, timestamps, [list(g) for g in self.grids], nets, image_to_time=image_to_time,
                                 use_global_trans=self.use_global_trans, deform_scales=deform_scales,
-                                first_frame_trainable=first_frame_trainable, plan=self.plan_for(xyz))
+                                first_frame_trainable=first_frame_trainable, plan=self.plan_for(xyz), image_plan=image_plan)

@@ -57,6 +57,7 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Union
 import torch
 
 from .arap import ArapGraph, MeshGraph, arap_energy
+from .cameras import CameraBatch
 from .deform4d import HexPlaneDeformation
 from .f32_stage import launch, launch_reduced, require_f32_cuda, require_index_cuda, require_shape
 from .hip_ops import _p
@@ -353,9 +354,10 @@ def frames_of_images(timestamps: torch.Tensor):
     return frames.contiguous(), image_to_time
 
 
-def render_batch(field: HexPlaneDeformation, gaussians: Gaussians, c2w: torch.Tensor, fovy: torch.Tensor, timestamps: torch.Tensor,
-                 height: int, width: int, bg, *, do_guidance: bool, first_frame_trainable: bool = False, keep_prob: float = 0.1,
-                 generator: Optional[torch.Generator] = None) -> RenderOutput:
+def render_batch(field: HexPlaneDeformation, gaussians: Gaussians, c2w: Optional[torch.Tensor], fovy: Optional[torch.Tensor],
+                 timestamps: Optional[torch.Tensor], height: Optional[int], width: Optional[int], bg, *, do_guidance: bool,
+                 first_frame_trainable: bool = False, keep_prob: float = 0.1, generator: Optional[torch.Generator] = None,
+                 cameras: Optional[CameraBatch] = None) -> RenderOutput:
     """``Gaussian4DBatchRenderer.batch_forward`` + ``DiffGaussian4D.forward`` for B images in one deformation call and one rasterizer call.
 
     ``c2w [B, 4, 4]``, ``fovy [B]`` and ``timestamps [B]`` / ``[B, 1]`` are per image, as the data module hands them over; ``bg [3]``.
@@ -364,18 +366,34 @@ def render_batch(field: HexPlaneDeformation, gaussians: Gaussians, c2w: torch.Te
     ``torch.rand(B, N, 1, generator=generator) < keep_prob`` on the device (a guidance step draws nothing); the rasterizer runs outside
     autocast.  Returns ``image [B, 3, H, W]`` (raw), ``comp_rgb [B, H, W, 3]`` (clamped; built on access), ``comp_mask`` / ``comp_depth
     [B, H, W, 1]``, ``radii [B, N]``, ``visibility_filter``, ``means3D`` / ``scales`` / ``rotations [B, N, .]``, the *unmasked* tensors
-    (advanced_4d.py:186-188), and ``opacities``."""
+    (advanced_4d.py:186-188), and ``opacities``.
+
+    ``cameras``: a ``cameras.CameraBatch`` in place of ``c2w`` / ``fovy`` / ``timestamps``, which must then be ``None`` (``ValueError``);
+    ``height`` / ``width`` may be ``None`` and must not contradict the batch's.  Its ``w2c``, ``full_proj``, ``campos``, ``tanfov``,
+    ``frames`` and ``image_to_time`` go to the field and the rasterizer as they are: no solver call, no ``torch.unique``, and no
+    synchronisation with the host before the rasterizer's own."""
     g = gaussians
-    frames, image_to_time = frames_of_images(timestamps)
+    if cameras is not None:
+        if c2w is not None or fovy is not None or timestamps is not None:
+            raise ValueError("cameras= replaces c2w, fovy and timestamps: pass None for all three")
+        if (height is not None and int(height) != cameras.height) or (width is not None and int(width) != cameras.width):
+            raise ValueError(f"height x width = {height} x {width}, but the cameras were made for {cameras.height} x {cameras.width}")
+        frames, image_to_time = cameras.frames, cameras.image_to_time
+    else:
+        frames, image_to_time = frames_of_images(timestamps)
+    plan = {} if cameras is None else dict(image_plan=cameras.image_plan)
     means, scales, rots = field(g.xyz, g.scaling, g.rotation, frames.float(), image_to_time, deform_scales=bool(do_guidance),
-                                first_frame_trainable=first_frame_trainable)
+                                first_frame_trainable=first_frame_trainable, **plan)
     m_in, s_in, r_in = means, scales, rots
     if not do_guidance:
         keep = (torch.rand(*means.shape[:2], 1, generator=generator, device=means.device) < keep_prob).float()
         m_in, s_in, r_in = _KeepMask.apply(keep, means, scales, rots)
     with torch.autocast("cuda", enabled=False):
-        w2c, proj, cam_p = get_cam_info_gaussian(c2w, fovy, fovy, znear=0.1, zfar=100)
-        tan = torch.tan(fovy.float().reshape(-1) / 2)
+        if cameras is not None:
+            w2c, proj, cam_p, tan, height, width = cameras.w2c, cameras.full_proj, cameras.campos, cameras.tanfov, cameras.height, cameras.width
+        else:
+            w2c, proj, cam_p = get_cam_info_gaussian(c2w, fovy, fovy, znear=0.1, zfar=100)
+            tan = torch.tan(fovy.float().reshape(-1) / 2)
         image, radii, depth, alpha = rasterize_gaussians(m_in, s_in, r_in, g.opacity, shs=g.shs, viewmatrix=w2c, projmatrix=proj, campos=cam_p,
                                                          tanfovx=tan, tanfovy=tan, image_height=int(height), image_width=int(width), bg=bg,
                                                          sh_degree=g.sh_degree)
@@ -394,7 +412,10 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
 
     ``batch``: the data module's resident tensors for all ``n_view * n_frame`` images, view-major (``rgb [., H, W, 3]``, ``mask
     [., H, W, 1]`` bool, ``c2w``, ``fovy``, ``timestamps``) and, for a guidance step, ``random_camera`` (``c2w``, ``fovy``, ``timestamps``,
-    ``height``, ``width``).  ``guidance``: ``comp_rgb [B, H, W, 3] -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound); a step with a
+    ``height``, ``width``).  Either may be a ``cameras.CameraBatch`` instead: ``batch["cameras"]`` (``data_view_cameras``) replaces ``c2w`` /
+    ``fovy`` / ``timestamps`` of the images, ``batch["random_camera"]`` may be one (``RandomCameraSampler.sample``); ``render`` then gets
+    ``cameras=`` and ``None`` for the three tensors, and only then.
+    ``guidance``: ``comp_rgb [B, H, W, 3] -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound); a step with a
     guidance callable is the reference's ``load_guidance: true``.  ``loss``: the lambdas under the reference's names (``lambda_rgb``,
     ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num``, for the mesh branch ``arap_K``, and the six regulariser weights
     ``lambda_tv_loss``, ``lambda_depth_tv_loss``, ``lambda_sparsity``, ``lambda_position``, ``lambda_opacity``, ``lambda_scales``); a
@@ -438,7 +459,7 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     if rgb.shape[0] != n_view * n_frame:
         raise ValueError(f"batch['rgb']: expected {n_view * n_frame} images (n_view * n_frame), got {rgb.shape[0]}")
     if reg["lambda_tv_loss"] or reg["lambda_depth_tv_loss"]:      # the last render's size, before anything is rendered
-        h, w = (batch["random_camera"]["height"], batch["random_camera"]["width"]) if do_guidance else rgb.shape[1:3]
+        h, w = (batch["random_camera"]["height"], batch["random_camera"]["width"]) if do_guidance else rgb.shape[1:3]   # dict or CameraBatch
         if h < 2 or w < 2:
             raise ValueError(f"a total-variation term needs H >= 2 and W >= 2, got {h} x {w} (the reference divides by zero)")
     frames = sampled_frames(global_step, n_frame, progressive_iter_per_frame, do_guidance=do_guidance, strategy=sample_strategy, rng=rng)
@@ -446,14 +467,21 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     gather = index.long()
     common = dict(do_guidance=do_guidance, first_frame_trainable=first_frame_trainable, keep_prob=keep_prob, generator=generator)
     bg0 = float(bg[0])
-    out = render(field, gaussians, batch["c2w"][gather], batch["fovy"][gather], batch["timestamps"][gather], rgb.shape[1], rgb.shape[2], bg,
-                 **common)
+    if isinstance(batch.get("cameras"), CameraBatch):             # the data views as a CameraBatch: gathered on the host
+        taken = batch["cameras"].take([v * n_frame + f for v in range(n_view) for f in frames])
+        out = render(field, gaussians, None, None, None, rgb.shape[1], rgb.shape[2], bg, cameras=taken, **common)
+    else:
+        out = render(field, gaussians, batch["c2w"][gather], batch["fovy"][gather], batch["timestamps"][gather], rgb.shape[1], rgb.shape[2], bg,
+                     **common)
     total, loss_rgb, loss_mask = masked_recon_loss(out["image"], out["alpha"], rgb, mask, index, bg=bg0, lambda_rgb=loss["lambda_rgb"],
                                                    lambda_mask=loss["lambda_mask"])
     terms = {"loss_rgb": loss_rgb * float(loss["lambda_rgb"]), "loss_mask": loss_mask * float(loss["lambda_mask"])}
     if do_guidance:
         cam = batch["random_camera"]
-        out = render(field, gaussians, cam["c2w"], cam["fovy"], cam["timestamps"], cam["height"], cam["width"], bg, **common)
+        if isinstance(cam, CameraBatch):
+            out = render(field, gaussians, None, None, None, cam.height, cam.width, bg, cameras=cam, **common)
+        else:
+            out = render(field, gaussians, cam["c2w"], cam["fovy"], cam["timestamps"], cam["height"], cam["width"], bg, **common)
         loss_sds = float(loss["lambda_sds"]) * guidance(out["comp_rgb"])
         total = total + loss_sds
         terms["loss_sds"] = loss_sds.detach()

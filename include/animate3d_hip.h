@@ -539,6 +539,39 @@ int a3d_mesh_vertex_gaussians_f32(a3d_stream_t stream, int Nv, int E, int C, con
 int a3d_gaussians_rigid_f32(a3d_stream_t stream, int N, const float* xyz_in, const float* scaling_in, const float* rotation_in,
                             const double* rot9, const double* quat4, double scale_factor, float* xyz, float* scaling, float* rotation);
 
+/* Camera batches of the 4-D stage (csrc/camera_batch.hip; contract in animate3d_amd/cameras.py), fp32 at the interface.  Replace the
+ * per-step CPU code of custom/threestudio-animate3d/data/uncond_hybrid.py (collate and the two eval datasets) and
+ * data/simple_multi_image.py:91-131, and the two solver calls of get_cam_info_gaussian.  One thread per camera, fp64 arithmetic, every
+ * output rounded to fp32 once; no atomics, no workspace, one launch.  Outputs per camera b, in the layout rasterize_gaussians takes:
+ * c2w [B, 4, 4] = [right, up, -lookat | pos] with lookat = normalize(centre - pos), right = normalize(lookat x up), up = normalize(right x
+ * lookat) (normalize: v / max(|v|, 1e-12)); w2c [B, 4, 4]: the inverse of c2w diag(1, -1, -1, 1), transposed (row-vector form);
+ * full_proj [B, 4, 4] = w2c projT with get_projection_matrix_gaussian's matrix for fovx = fovy, znear, zfar; campos [B, 3] = pos;
+ * tanfov [B] = tan(fovy / 2).
+ *   a3d_cameras_spherical_f32  pos = distance (cos e cos a, cos e sin a, sin e) for elevation e, azimuth a; angles and fovy are given in
+ *                          units of angle_unit radians (1: radians; pi / 180: degrees, converted in fp64).  perturb [B, 9] or NULL:
+ *                          (offset added to pos, centre, offset added to the up vector (0, 0, 1)); NULL: centre 0, up (0, 0, 1)
+ *   a3d_cameras_random_f32  collate (uncond_hybrid.py:195-304) on explicit draws for B = R n_view total_frame cameras, object-major, then
+ *                          view, then frame: obj [R, 5] uniform (elevation, azimuth, fovy, distance, zoom), pert_u [B, 3] uniform,
+ *                          pert_n [B, 6] normal (centre, up).  ranges10: HOST pointer to 10 doubles, (lo, hi) of elevation, azimuth and
+ *                          fovy in degrees, of the distance and of the zoom.  elev_mode 0: elevation uniform in degrees; 1: uniform
+ *                          on the sphere, asin(u (sin hi - sin lo) + sin lo).  azimuth of view v = (u + v) / n_view (hi - lo) + lo;
+ *                          distance *= 1 / tan(fovy / 2) with relative_radius, before fovy *= zoom; pos += pert_u 2 camera_perturb -
+ *                          camera_perturb, centre = pert_n[:3] center_perturb, up = (0, 0, 1) + pert_n[3:] up_perturb.  Also written:
+ *                          elevation_deg, azimuth_deg, fovy (radians, after the zoom), camera_distances [B]
+ *   a3d_cameras_from_c2w_f32  any invertible c2w [B, 4, 4] and fovy [B] (radians): the 4 x 4 inverse by the adjugate; campos = c2w[:3, 3]
+ * A3D_EINVAL before any launch for: a NULL pointer other than perturb, a pointer that is not 4-byte aligned, B or R or n_view or
+ * total_frame <= 0, more than 2^24 cameras, elev_mode other than 0 / 1, a non-finite range or perturbation, angle_unit not a positive
+ * finite number, znear / zfar not finite with 0 < znear < zfar. */
+int a3d_cameras_spherical_f32(a3d_stream_t stream, int B, const float* elevation, const float* azimuth, const float* distance,
+                              const float* fovy, const float* perturb, double angle_unit, double znear, double zfar, float* c2w, float* w2c,
+                              float* full_proj, float* campos, float* tanfov);
+int a3d_cameras_random_f32(a3d_stream_t stream, int R, int n_view, int total_frame, const float* obj, const float* pert_u,
+                           const float* pert_n, const double* ranges10, int elev_mode, int relative_radius, double camera_perturb,
+                           double center_perturb, double up_perturb, double znear, double zfar, float* c2w, float* w2c, float* full_proj,
+                           float* campos, float* tanfov, float* elevation_deg, float* azimuth_deg, float* fovy, float* camera_distances);
+int a3d_cameras_from_c2w_f32(a3d_stream_t stream, int B, const float* c2w, const float* fovy, double znear, double zfar, float* w2c,
+                             float* full_proj, float* campos, float* tanfov);
+
 /* Reconstruction loss of the 4-D stage (csrc/recon_loss.hip; contract in animate3d_amd/stage4d.py, masked_recon_loss), fp32.  Replaces the
  * val[sampled_idx] copies, the mask compositing and the two F.mse_loss of custom/threestudio-animate3d/systems/animate3d.py:160-184 and the
  * clamp of diff_gaussian_rasterizer_advanced_4d.py:180.  image [B, 3, H, W] planar and unclamped, alpha [B, H, W], gt_rgb [S, H, W, 3]
