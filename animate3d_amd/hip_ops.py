@@ -141,6 +141,8 @@ _SIGNATURES = {
     "a3d_mesh_vertex_gaussians_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
                                               c_int, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_gaussians_rigid_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
+    # mesh export (csrc/mesh_export.hip): fp32 only, no storage twin
+    "a3d_mesh_vertex_normals_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # camera batches of the 4-D stage (csrc/camera_batch.hip): fp32 only, no storage twins; ranges10 is a host pointer to doubles
     "a3d_cameras_spherical_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "a3d_cameras_random_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_f64,

@@ -539,6 +539,21 @@ int a3d_mesh_vertex_gaussians_f32(a3d_stream_t stream, int Nv, int E, int C, con
 int a3d_gaussians_rigid_f32(a3d_stream_t stream, int N, const float* xyz_in, const float* scaling_in, const float* rotation_in,
                             const double* rot9, const double* quat4, double scale_factor, float* xyz, float* scaling, float* rotation);
 
+/* Mesh export (csrc/mesh_export.hip; contract in animate3d_amd/mesh_export.py), fp32 at the interface.  The per-frame vertex normals of
+ * the animated mesh that replaces tools/mesh_animation/export_animated_mesh.py (which leaves them to Blender).
+ *   a3d_mesh_vertex_normals_f32  one thread per (frame t, vertex v) of pos [T, Nv, 3] over v's corner list order [C] / starts [Nv + 1]
+ *                          (corner c is entry c of faces [F, 3] flattened, C = 3 F; the list a3d_mesh_vertex_gaussians_f32 reads):
+ *                          nrm [T, Nv, 3] = normalize(sum over v's corners c, in the list's order, of u x w) with f = c / 3, k = c - 3 f,
+ *                          a = faces[c], b = faces[3 f + (k + 1) % 3], d = faces[3 f + (k + 2) % 3], u = P_t[b] - P_t[a], w = P_t[d] -
+ *                          P_t[a]: area-weighted, a face with two equal corners adds exactly 0.  Differences, products, the sum and
+ *                          the normalisation are fp64 without contraction, the result is rounded to fp32 once; where the squared
+ *                          length of the sum is not > 0 or not finite, nrm = (0, 0, 1).  A3D_EINVAL before any launch for: T < 1,
+ *                          Nv < 1, C < 3, C % 3 != 0, T Nv 3 >= 2^31, a NULL pointer, a pointer that is not 4-byte aligned.  The
+ *                          indices the kernel reads (starts, order, faces) are clamped to their arrays.  No atomics, no workspace,
+ *                          no host synchronisation, one launch; bitwise reproducible and independent of the launch geometry */
+int a3d_mesh_vertex_normals_f32(a3d_stream_t stream, int T, int Nv, int C, const float* pos, const int* faces, const int* order,
+                                const int* starts, float* nrm);
+
 /* Camera batches of the 4-D stage (csrc/camera_batch.hip; contract in animate3d_amd/cameras.py), fp32 at the interface.  Replace the
  * per-step CPU code of custom/threestudio-animate3d/data/uncond_hybrid.py (collate and the two eval datasets) and
  * data/simple_multi_image.py:91-131, and the two solver calls of get_cam_info_gaussian.  One thread per camera, fp64 arithmetic, every
