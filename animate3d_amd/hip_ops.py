@@ -24,6 +24,15 @@ class _RowMapC(ctypes.Structure):
     _fields_ = [("gdiv", c_i64), ("ga", c_i64), ("gb", c_i64), ("seg_len", c_i64), ("seg_stride", c_i64), ("ld", c_i64)]
 
 
+class StageAdamEntry(ctypes.Structure):
+    """a3d_stage_adam_entry of include/animate3d_hip.h: one tensor of a3d_stage_adam_f32's host table."""
+    _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("step", c_vp), ("n", c_i64), ("lr", c_f64)]
+
+
+STAGE_ADAM_MAX_TENSORS = 32                                   # A3D_STAGE_ADAM_MAX_TENSORS
+STAGE_ADAM_BEGIN, STAGE_ADAM_CHECK, STAGE_ADAM_UPDATE = 1, 2, 4
+
+
 @dataclass(frozen=True)
 class RowMap:
     """row(g, s) = (g // gdiv) * ga + (g % gdiv) * gb + (s // seg_len) * seg_stride + s % seg_len
@@ -156,6 +165,8 @@ _SIGNATURES = {
     "a3d_image_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "a3d_gaussian_reg_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_gaussian_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    # the optimiser step of the 4-D stage (csrc/stage_optim.hip): fp32 only, no storage twin; table is a host pointer to StageAdamEntry
+    "a3d_stage_adam_f32": (c_int, [c_vp, c_vp, c_int, c_f64, c_f64, c_f64, c_int, c_vp]),
     # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins
     "a3d_clip_preprocess_lds_limit": (c_i64, []),
     "a3d_clip_preprocess": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,

@@ -47,7 +47,8 @@ opacity_term)``: the six terms of animate3d.py:256-296, one forward and one back
 ``sampled_frames`` / ``sampled_image_index`` restate the progressive frame schedule (animate3d.py:134-157); ``render_batch`` is the
 renderer for a whole batch with the policy of advanced_4d.py:130-162; ``training_step`` is the step, with either ARAP branch (the k-NN
 graph or the mesh's connectivity); ``vertex_trajectory`` the deformed means of every frame (``save_gaussian_trajectory``);
-``field_param_groups`` the optimiser groups of geometry/gaussian_4d.py:344-391.
+``field_param_groups`` the optimiser groups of geometry/gaussian_4d.py:344-391; ``fit`` the loop around the step, for any optimiser
+(``stage_optim.StageAdam`` is the stage's own).
 """
 from __future__ import annotations
 
@@ -552,3 +553,57 @@ def field_param_groups(field: HexPlaneDeformation, *, delta_xyz_network_lr: floa
             continue
         groups.append({"params": params, "lr": float(rates[name]), "name": name})
     return groups
+
+
+def fit(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict, optimizer, *, steps: int, start_step: int = 0, sampler=None,
+        generator: Optional[torch.Generator] = None, rng=random, **step_kwargs) -> Dict[str, torch.Tensor]:
+    """``steps`` optimisation steps ``s = start_step, start_step + 1, ...`` of ``training_step(field, gaussians, batch, **step_kwargs)``, in
+    the reference's order (``forward`` sets the rates before it renders, animate3d.py:116; Lightning steps afterwards).  Each step, on a
+    shallow copy of ``batch``:
+
+    1. with a ``sampler`` (``cameras.RandomCameraSampler``): ``sampler.update_step(s)`` and, when ``step_kwargs`` holds a ``guidance``,
+       ``batch["random_camera"] = sampler.sample(generator, rng=rng)``;
+    2. ``optimizer.update_learning_rate(s)`` where the optimiser has that method (``stage_optim.StageAdam``; any torch optimiser works
+       without it);
+    3. ``optimizer.zero_grad(set_to_none=True)``;
+    4. ``out = training_step(..., global_step=s, generator=generator, rng=rng)``;
+    5. ``out["loss"].backward()``;
+    6. ``optimizer.step()``.
+
+    Returns one ``[steps]`` fp32 device tensor per term ``training_step`` returned; a term that a step did not return is NaN there.  With
+    an optimiser that has a ``skipped`` flag (``StageAdam``) the result also holds ``"skipped"``: 1 where the step was dropped for a
+    non-finite gradient.  Logging is device-to-device copies: the loop adds no synchronisation with the host.  Training in segments
+    (validate, checkpoint, continue) is another call with the next ``start_step``; there are no callbacks."""
+    steps, start_step = int(steps), int(start_step)
+    if steps < 1 or start_step < 0:
+        raise ValueError(f"fit: steps = {steps}, start_step = {start_step}: expected steps >= 1 and start_step >= 0")
+    for name in ("global_step", "generator", "rng"):
+        if name in step_kwargs:
+            raise TypeError(f"fit: {name} is the loop's to pass")
+    update_rates = getattr(optimizer, "update_learning_rate", None)
+    skipped = getattr(optimizer, "skipped", None)
+    logs: Dict[str, torch.Tensor] = {}
+
+    def log(key, i, value):
+        if key not in logs:
+            logs[key] = torch.full((steps,), float("nan"), dtype=torch.float32, device=value.device)
+        logs[key][i].copy_(value.detach().reshape(()))
+
+    for i in range(steps):
+        s = start_step + i
+        step_batch = dict(batch)
+        if sampler is not None:
+            sampler.update_step(s)
+            if step_kwargs.get("guidance") is not None:
+                step_batch["random_camera"] = sampler.sample(generator, rng=rng)
+        if update_rates is not None:
+            update_rates(s)
+        optimizer.zero_grad(set_to_none=True)
+        out = training_step(field, gaussians, step_batch, global_step=s, generator=generator, rng=rng, **step_kwargs)
+        out["loss"].backward()
+        optimizer.step()
+        for key, value in out.items():
+            log(key, i, value)
+        if skipped is not None:
+            log("skipped", i, skipped)
+    return logs

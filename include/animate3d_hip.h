@@ -646,6 +646,46 @@ int a3d_gaussian_reg_bwd_f32(a3d_stream_t stream, int B, int N, const float* mea
                              float coef_scales, float coef_opacity, const float* grad_out, float* d_means, float* d_scales,
                              float* d_opacity);
 
+/* The optimiser step of the 4-D stage (csrc/stage_optim.hip; contract in animate3d_amd/stage_optim.py, StageAdam), fp32.  Replaces
+ * torch.optim.Adam(l, lr=0.0, eps=1e-15) of custom/threestudio-animate3d/geometry/gaussian_4d.py:391 and the step that Lightning's
+ * GradScaler drops when a gradient holds an inf or a NaN.
+ *   a3d_stage_adam_f32  table: HOST pointer to count entries, 1 <= count <= A3D_STAGE_ADAM_MAX_TENSORS; it is copied into the kernels'
+ *                       arguments, nothing is copied to the device.  Entry t: parameter p, gradient g, moments m and v of n fp32
+ *                       elements each, the tensor's own step (one fp32 on the device, an exact integer) and its own rate lr.  No two
+ *                       entries may overlap.  flag: one int32 on the device.  phases, a sum of
+ *                         A3D_STAGE_ADAM_BEGIN   flag = 0
+ *                         A3D_STAGE_ADAM_CHECK   flag = 1 where any element of any g of the table is an inf or a NaN
+ *                         A3D_STAGE_ADAM_UPDATE  where flag == 0: per element, with k = step + 1,
+ *                                                  m' = beta1 m + (1 - beta1) g,  v' = beta2 v + (1 - beta2) g^2,
+ *                                                  p' = p - (lr / (1 - beta1^k)) m' / (sqrt(v') / sqrt(1 - beta2^k) + eps)
+ *                                                (torch.optim.Adam without amsgrad, weight decay or maximize) in fp64 on the fp32
+ *                                                loads, without contraction, the update from the unrounded m' and v', each of p', m',
+ *                                                v' rounded to fp32 once; then step += 1 for every tensor.  Where flag != 0: nothing
+ *                                                is written, the steps included
+ *                       run in this order.  All three in one call is the whole step of up to A3D_STAGE_ADAM_MAX_TENSORS tensors.  More
+ *                       tensors: BEGIN | CHECK with the first table, CHECK with every other, then UPDATE with each, on one stream;
+ *                       the check then covers every tensor before any is updated, and flag reads 1 (skipped) or 0 afterwards.
+ *                       At most four launches per call, whatever count is; no atomics, no workspace but the flag, no host
+ *                       synchronisation; no result depends on the order in which blocks run.  4-byte accesses.
+ * A3D_EINVAL before any launch for: table or flag NULL, count < 1 or > A3D_STAGE_ADAM_MAX_TENSORS, phases 0 or with another bit, beta1 or
+ * beta2 outside [0, 1), eps negative or not finite, and in any entry a NULL pointer, a pointer that is not 4-byte aligned, n < 1, lr
+ * negative or not finite, or more than 2^31 - 1 blocks of 1 024 elements in all. */
+#define A3D_STAGE_ADAM_MAX_TENSORS 32
+#define A3D_STAGE_ADAM_BEGIN 1
+#define A3D_STAGE_ADAM_CHECK 2
+#define A3D_STAGE_ADAM_UPDATE 4
+typedef struct a3d_stage_adam_entry {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  float* step;
+  int64_t n;
+  double lr;
+} a3d_stage_adam_entry;
+int a3d_stage_adam_f32(a3d_stream_t stream, const a3d_stage_adam_entry* table, int count, double beta1, double beta2, double eps,
+                       int phases, int* flag);
+
 /* CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip; contract in animate3d_amd/clip.py, preprocess_frames).
  * Replaces the device -> host -> PIL -> CLIPImageProcessor -> device round trip of animatemv_guidance.py:546-555 / utils/util.py:268-287,
  * bit-equal to it: (uint8)(v * 255.0f), Pillow's 8-bit bicubic resampler (integer, 22 precision bits, horizontal then vertical pass, a
