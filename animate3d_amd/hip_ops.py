@@ -160,6 +160,11 @@ _SIGNATURES = {
     # reconstruction loss of the 4-D stage (csrc/recon_loss.hip): fp32 only, no storage twins
     "a3d_recon_loss_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_recon_loss_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "a3d_recon_loss_rgba8_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
+    "a3d_recon_loss_rgba8_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    # frames of the 4-D stage (csrc/stage_frames.hip): 8-bit RGBA in and out, no storage twins
+    "a3d_frames_unpack_u8": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "a3d_frames_pack_u8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     # regularisers of the 4-D stage's step (csrc/stage_reg.hip): fp32 only, no storage twins
     "a3d_image_reg_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_image_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),

@@ -25,6 +25,10 @@ is no torch fallback.
   layout the rasterizer's backward reads.  The upstream gradient is read on the device: neither direction synchronises with the host.
   Without a gradient to compute nothing is saved.
 
+``masked_recon_loss_rgba8(image, alpha, gt_rgba8, index=None, *, bg, lambda_rgb, lambda_mask)``: the same loss on the same two kernels,
+reading ``gt_rgba8 [S, H, W, 4]`` uint8 (``frames.FrameSet``) as ``byte / 255.0f`` and ``alpha byte >= 128``: bit-equal results, 4 bytes of
+ground truth a pixel where ``gt_rgb`` + ``gt_mask`` are 13.
+
 ``image_regularizers(image, depth, alpha, *, lambda_tv, lambda_depth_tv, lambda_sparsity) -> (loss, tv, depth_tv, sparsity)`` and
 ``gaussian_regularizers(means, scales, scaling, opacity, *, lambda_position, lambda_scales, lambda_opacity) -> (loss, position, scale_sum,
 opacity_term)``: the six terms of animate3d.py:256-296, one forward and one backward kernel per call.
@@ -85,28 +89,48 @@ def _empty_grads(need, shapes, device):                          # a gradient fo
 
 
 class _MaskedReconLoss(torch.autograd.Function):
+    """``gt``: ``(gt_rgb, gt_mask)`` for the fp32 entry points, ``(gt_rgba8,)`` for the 8-bit ones; everything else is one code."""
+
     @staticmethod
-    def forward(ctx, image, alpha, gt_rgb, gt_mask, index, bg, lambda_rgb, lambda_mask):
+    def forward(ctx, image, alpha, index, bg, lambda_rgb, lambda_mask, *gt):
         B, _, H, W = image.shape
         img, alp = image.detach().contiguous(), alpha.detach().contiguous()
-        out = launch_reduced("a3d_recon_loss_f32", image.device, (B, H, W), (_p(img), _p(alp), _p(gt_rgb), _p(gt_mask), _p(index), bg,
+        ctx.entry = "a3d_recon_loss" + ("_rgba8" if len(gt) == 1 else "")
+        out = launch_reduced(ctx.entry + "_f32", image.device, (B, H, W), (_p(img), _p(alp), *(_p(t) for t in gt), _p(index), bg,
                              lambda_rgb, lambda_mask), 2, (B, H * W, PIXELS_PER_BLOCK), 3)
         ctx.need = tuple(ctx.needs_input_grad[:2])
         if any(ctx.need):
-            ctx.save_for_backward(img, alp, gt_rgb, gt_mask, index)
+            ctx.save_for_backward(img, alp, index, *gt)
             ctx.consts = (bg, 2.0 * lambda_rgb / (3.0 * B * H * W), 2.0 * lambda_mask / (1.0 * B * H * W), alpha.shape)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        img, alp, gt_rgb, gt_mask, index = ctx.saved_tensors
+        img, alp, index, *gt = ctx.saved_tensors
         bg, coef_rgb, coef_mask, alpha_shape = ctx.consts
         B, _, H, W = img.shape
         g = _upstream(d_out)
         d_image, d_alpha = _empty_grads(ctx.need, (img.shape, alpha_shape), img.device)
-        launch("a3d_recon_loss_bwd_f32", img.device, B, H, W, _p(img), _p(alp), _p(gt_rgb), _p(gt_mask), _p(index), bg, coef_rgb, coef_mask,
+        launch(ctx.entry + "_bwd_f32", img.device, B, H, W, _p(img), _p(alp), *(_p(t) for t in gt), _p(index), bg, coef_rgb, coef_mask,
                _p(g), _p(d_image), _p(d_alpha))
-        return d_image, d_alpha, None, None, None, None, None, None
+        return (d_image, d_alpha, None, None, None, None, *(None for _ in gt))
+
+
+def _recon_index(index, S: int, B: int, dev):
+    """``index`` as the kernels take it: int32 ``[B]`` on ``dev``, or ``None``.  A list or CPU tensor is range-checked, a device tensor is not."""
+    if index is None:
+        return None
+    if not (isinstance(index, torch.Tensor) and index.is_cuda):
+        index = torch.as_tensor(index)
+        if index.dtype not in (torch.int32, torch.int64) or index.dim() != 1:
+            raise ValueError("index: a 1-D int32 / int64 tensor or a list of ints")
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= S):
+            raise IndexError(f"index: values must lie in [0, {S}), got [{int(index.min())}, {int(index.max())}]")
+        index = index.to(dev)
+    require_index_cuda("index", index)
+    if tuple(index.shape) != (B,):
+        raise ValueError(f"index: expected [{B}], got {tuple(index.shape)}")
+    return index.to(torch.int32).contiguous()
 
 
 def masked_recon_loss(image: torch.Tensor, alpha: torch.Tensor, gt_rgb: torch.Tensor, gt_mask: torch.Tensor, index=None, *, bg: float,
@@ -133,23 +157,39 @@ def masked_recon_loss(image: torch.Tensor, alpha: torch.Tensor, gt_rgb: torch.Te
         raise RuntimeError("gt_mask: expected a CUDA tensor (no CPU fallback)")
     if gt_rgb.requires_grad:
         raise NotImplementedError("gt_rgb.requires_grad: the ground truth is data")
-    dev = image.device
-    if index is not None:
-        if not (isinstance(index, torch.Tensor) and index.is_cuda):
-            index = torch.as_tensor(index)
-            if index.dtype not in (torch.int32, torch.int64) or index.dim() != 1:
-                raise ValueError("index: a 1-D int32 / int64 tensor or a list of ints")
-            if index.numel() and (int(index.min()) < 0 or int(index.max()) >= S):
-                raise IndexError(f"index: values must lie in [0, {S}), got [{int(index.min())}, {int(index.max())}]")
-            index = index.to(dev)
-        require_index_cuda("index", index)
-        if tuple(index.shape) != (B,):
-            raise ValueError(f"index: expected [{B}], got {tuple(index.shape)}")
-        index = index.to(torch.int32).contiguous()
+    index = _recon_index(index, S, B, image.device)
     gt = gt_rgb.detach().contiguous()                            # the data module's tensors are contiguous: no copy
     mask = gt_mask.contiguous()
     mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    out = _MaskedReconLoss.apply(image, alpha, gt, mask, index, float(bg), float(lambda_rgb), float(lambda_mask))
+    out = _MaskedReconLoss.apply(image, alpha, index, float(bg), float(lambda_rgb), float(lambda_mask), gt, mask)
+    return out[0], out[1].detach(), out[2].detach()
+
+
+def masked_recon_loss_rgba8(image: torch.Tensor, alpha: torch.Tensor, gt_rgba8: torch.Tensor, index=None, *, bg: float, lambda_rgb: float,
+                            lambda_mask: float):
+    """``masked_recon_loss`` against 8-bit ground truth: ``gt_rgba8 [S, H, W, 4]`` uint8 (``frames.FrameSet.rgba8``) in place of ``gt_rgb`` and
+    ``gt_mask``, 4 bytes a pixel where those are 13.  The kernels are the same two with another reader of the ground truth: colour
+    ``byte / 255.0f`` by IEEE division and inside ``alpha byte >= 128``, so the three losses and both gradients are bit-equal to
+    ``masked_recon_loss`` on ``gt_rgba8[..., :3].float() / 255`` and ``gt_rgba8[..., 3:] >= 128`` (the reference's tensors,
+    data/simple_multi_image.py:205-215).  Everything else is that function's contract: ``index``, the reduction, a backward that recomputes
+    from the inputs and saves nothing else."""
+    for name, t in (("image", image), ("alpha", alpha), ("gt_rgba8", gt_rgba8)):
+        require_shape(name, t)
+    if gt_rgba8.dtype != torch.uint8:
+        raise TypeError(f"gt_rgba8: expected a uint8 tensor, got {gt_rgba8.dtype}")
+    require_shape("image", image, ("B", 3, "H", "W"), non_empty=True)
+    B, _, H, W = image.shape
+    require_shape("alpha", alpha, (B, 1, H, W), (B, H, W))
+    require_shape("gt_rgba8", gt_rgba8, ("S", H, W, 4))
+    S = gt_rgba8.shape[0]
+    if index is None and S != B:
+        raise ValueError(f"index=None compares image b with frame b: needs S == B, got S = {S}, B = {B}")
+    require_f32_cuda("image", image)
+    require_f32_cuda("alpha", alpha)
+    if not gt_rgba8.is_cuda:
+        raise RuntimeError("gt_rgba8: expected a CUDA tensor (no CPU fallback)")
+    index = _recon_index(index, S, B, image.device)
+    out = _MaskedReconLoss.apply(image, alpha, index, float(bg), float(lambda_rgb), float(lambda_mask), gt_rgba8.contiguous())
     return out[0], out[1].detach(), out[2].detach()
 
 
@@ -412,7 +452,8 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     """``Animate3DSystem.training_step``: the losses of one step; the caller runs ``out["loss"].backward()`` and the optimiser.
 
     ``batch``: the data module's resident tensors for all ``n_view * n_frame`` images, view-major (``rgb [., H, W, 3]``, ``mask
-    [., H, W, 1]`` bool, ``c2w``, ``fovy``, ``timestamps``) and, for a guidance step, ``random_camera`` (``c2w``, ``fovy``, ``timestamps``,
+    [., H, W, 1]`` bool, or in their place ``rgba8 [., H, W, 4]`` uint8 / a ``frames.FrameSet``, read by ``masked_recon_loss_rgba8``: the
+    same bits from 4 bytes a pixel; both or neither is a ``ValueError`` before anything is launched; ``c2w``, ``fovy``, ``timestamps``) and, for a guidance step, ``random_camera`` (``c2w``, ``fovy``, ``timestamps``,
     ``height``, ``width``).  Either may be a ``cameras.CameraBatch`` instead: ``batch["cameras"]`` (``data_view_cameras``) replaces ``c2w`` /
     ``fovy`` / ``timestamps`` of the images, ``batch["random_camera"]`` may be one (``RandomCameraSampler.sample``); ``render`` then gets
     ``cameras=`` and ``None`` for the three tensors, and only then.
@@ -456,9 +497,14 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
             raise ValueError(f"graph: a mesh of {graph.Nv} vertices for {gaussians.xyz.shape[0]} Gaussians")
         if "arap_K" not in loss:
             raise ValueError("a MeshGraph needs loss['arap_K']: the number of neighbours drawn per vertex and step")
-    rgb, mask = batch["rgb"], batch["mask"]
+    rgba8 = batch.get("rgba8")
+    rgba8 = getattr(rgba8, "rgba8", rgba8)                       # a frames.FrameSet stands for its tensor
+    if (rgba8 is not None) == ("rgb" in batch or "mask" in batch):
+        raise ValueError("batch: the ground truth is either 'rgba8' (uint8 [., H, W, 4], or a frames.FrameSet) or 'rgb' and 'mask', got "
+                         + ("both" if rgba8 is not None else "neither"))
+    rgb, mask = (rgba8, None) if rgba8 is not None else (batch["rgb"], batch["mask"])      # rgb: whichever holds the images' shape
     if rgb.shape[0] != n_view * n_frame:
-        raise ValueError(f"batch['rgb']: expected {n_view * n_frame} images (n_view * n_frame), got {rgb.shape[0]}")
+        raise ValueError(f"batch['{'rgb' if rgba8 is None else 'rgba8'}']: expected {n_view * n_frame} images (n_view * n_frame), got {rgb.shape[0]}")
     if reg["lambda_tv_loss"] or reg["lambda_depth_tv_loss"]:      # the last render's size, before anything is rendered
         h, w = (batch["random_camera"]["height"], batch["random_camera"]["width"]) if do_guidance else rgb.shape[1:3]   # dict or CameraBatch
         if h < 2 or w < 2:
@@ -474,8 +520,12 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     else:
         out = render(field, gaussians, batch["c2w"][gather], batch["fovy"][gather], batch["timestamps"][gather], rgb.shape[1], rgb.shape[2], bg,
                      **common)
-    total, loss_rgb, loss_mask = masked_recon_loss(out["image"], out["alpha"], rgb, mask, index, bg=bg0, lambda_rgb=loss["lambda_rgb"],
-                                                   lambda_mask=loss["lambda_mask"])
+    if rgba8 is not None:
+        total, loss_rgb, loss_mask = masked_recon_loss_rgba8(out["image"], out["alpha"], rgba8, index, bg=bg0, lambda_rgb=loss["lambda_rgb"],
+                                                             lambda_mask=loss["lambda_mask"])
+    else:
+        total, loss_rgb, loss_mask = masked_recon_loss(out["image"], out["alpha"], rgb, mask, index, bg=bg0, lambda_rgb=loss["lambda_rgb"],
+                                                       lambda_mask=loss["lambda_mask"])
     terms = {"loss_rgb": loss_rgb * float(loss["lambda_rgb"]), "loss_mask": loss_mask * float(loss["lambda_mask"])}
     if do_guidance:
         cam = batch["random_camera"]

@@ -608,6 +608,35 @@ int a3d_recon_loss_bwd_f32(a3d_stream_t stream, int B, int H, int W, const float
                            const uint8_t* gt_mask, const int* index, float bg, float coef_rgb, float coef_mask, const float* grad_out,
                            float* d_image, float* d_alpha);
 
+/* The same pair on 8-bit ground truth: gt_rgba8 [S, H, W, 4] bytes (r, g, b, a) in place of gt_rgb and gt_mask.  The kernels are the two
+ * above with another reader of the ground truth, the only thing that differs: colour = (float)byte / 255.0f by IEEE division, inside =
+ * alpha byte >= 128 (byte / 255.0f > 0.5f).  Against gt_rgb = byte / 255.0f and gt_mask = alpha byte >= 128 every output is bit-equal
+ * to the pair above.  Geometry, partial count, summation order, index and every other rule are theirs.  gt_rgba8 is 4-byte aligned at
+ * least (A3D_EINVAL otherwise, before the first HIP call); where H W % 4 == 0 and it and every float pointer are 16-byte aligned, four
+ * pixels are read as one 16-byte load. */
+int a3d_recon_loss_rgba8_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* alpha, const uint8_t* gt_rgba8,
+                             const int* index, float bg, double lambda_rgb, double lambda_mask, float* partials, int64_t n_partials,
+                             float* out);
+int a3d_recon_loss_rgba8_bwd_f32(a3d_stream_t stream, int B, int H, int W, const float* image, const float* alpha, const uint8_t* gt_rgba8,
+                                 const int* index, float bg, float coef_rgb, float coef_mask, const float* grad_out, float* d_image,
+                                 float* d_alpha);
+
+/* Frames of the 4-D stage (csrc/stage_frames.hip; contract in animate3d_amd/frames.py): 8-bit RGBA ground truth in, test renders out.
+ * Replace the CPU arithmetic of custom/threestudio-animate3d/data/simple_multi_image.py:205-215 and systems/animate3d.py:441-445.
+ *   a3d_frames_unpack_u8  rgba8 [S, h, w, 4] bytes and an integer reduction factor k, 1 <= k <= 16, h = k H, w = k W.  Per output pixel and
+ *                         channel, alpha included: q = (2 sum + k^2) / (2 k^2) in integers over the k x k source bytes, the exact mean
+ *                         rounded half up (k = 1: the byte itself).  Outputs, each may be NULL but not all: out8 [S, H, W, 4] the bytes q;
+ *                         rgb [S, H, W, 3] fp32 = (float)q / 255.0f by IEEE division, never a multiply by a reciprocal; mask [S, H, W]
+ *                         bytes 0 / 1 = q_alpha >= 128, which is q / 255.0f > 0.5f.  One thread per output pixel, one 4-byte load per
+ *                         source pixel
+ *   a3d_frames_pack_u8    image [B, 3, H, W] planar and alpha [B, H, W] fp32 -> rgba8 [B, H, W, 4] bytes: (uint8)(clamp(v, 0, 1) * 255.0f)
+ *                         in fp32, truncating, what (rgba_img * 255).astype(np.uint8) gives for the clamped comp_rgb.  alpha is clamped
+ *                         as well (comp_mask is not clamped in the reference; a rasterizer alpha lies in [0, 1]); a NaN gives 0
+ * A3D_EINVAL before any launch for: a NULL input, no output, an extent <= 0, k outside 1 .. 16, h % k or w % k != 0, 2^39 pixels or more
+ * (S h w, B H W), a pointer other than mask that is not 4-byte aligned.  No atomics, no workspace, no host synchronisation, one launch. */
+int a3d_frames_unpack_u8(a3d_stream_t stream, int S, int h, int w, int k, const uint8_t* rgba8, uint8_t* out8, float* rgb, uint8_t* mask);
+int a3d_frames_pack_u8(a3d_stream_t stream, int B, int H, int W, const float* image, const float* alpha, uint8_t* rgba8);
+
 /* Regularisers of the 4-D stage's step (csrc/stage_reg.hip; contract in animate3d_amd/stage4d.py, image_regularizers and
  * gaussian_regularizers), fp32.  Replace the torch chains of custom/threestudio-animate3d/systems/animate3d.py:256-296 over tv_loss
  * (threestudio/utils/loss.py:8-16).  image [B, 3, H, W] planar and unclamped, depth and alpha [B, H, W]; means [B, N, 3]; scales: image b's
