@@ -21,7 +21,6 @@
 #include "f32_common.h"
 #include "loss_reduce.h"
 
-#ifndef A3D_STORAGE_F16
 #include <math.h>
 
 namespace {
@@ -449,5 +448,3 @@ extern "C" int a3d_mesh_sample_neighbours(a3d_stream_t stream, int Nv, int E, co
   mesh_sample_kernel<<<blocks_for(Nv), 256, 0, (hipStream_t)stream>>>(Nv, E, row_start, col, K, seed, nn_idx);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -10,7 +10,6 @@
 // w2c projT, campos, tanfov, in the layout rasterize_gaussians takes.
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 #include <math.h>
 
 namespace {
@@ -255,5 +254,3 @@ extern "C" int a3d_cameras_from_c2w_f32(a3d_stream_t stream, int B, const float*
   from_c2w_kernel<<<blocks_for(B, 64), 64, 0, (hipStream_t)stream>>>(B, c2w, fovy, znear, zfar, o);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -14,8 +14,6 @@
 // No atomics, no dependence on launch geometry: every output element is written once by one thread from integers.
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16      // fp32 / integer arithmetic; the 16-bit outputs are chosen by a run-time dtype code: one copy in the library
-
 namespace {
 
 constexpr int CLIP_PRECISION_BITS = 22;               // Pillow: 32 - 8 - 2
@@ -163,5 +161,3 @@ extern "C" int a3d_clip_preprocess(a3d_stream_t stream, const float* rgb, int n_
   clip_preprocess_kernel<<<(unsigned)(n_img * n_tiles), CLIP_THREADS, (size_t)((lds + 15) / 16 * 16), (hipStream_t)stream>>>(a);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -15,14 +15,17 @@ typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 #define A3D_DEV static __device__ __forceinline__
 
 // ---- the 16-bit activation / weight type of this build of the kernels
-// Every kernel source is compiled twice (animate3d_amd/build.py): as is for bf16 storage and with -DA3D_STORAGE_F16 for IEEE fp16
-// storage (the dtype the reference's 4D-SDS caller runs the UNet in, animatemv_guidance.py:339-346).  Arithmetic is the same
-// in both: fp32 accumulation, statistics and softmax; only the load / store conversions, the MFMA opcode
+// A twin source — every .hip that animate3d_amd/build.py does not list in SINGLE_STORAGE — is compiled twice: as is for bf16 storage and
+// with -DA3D_STORAGE_F16 for IEEE fp16 storage (the dtype the reference's 4D-SDS caller runs the UNet in, animatemv_guidance.py:339-346).
+// Arithmetic is the same in both: fp32 accumulation, statistics and softmax; only the load / store conversions, the MFMA opcode
 // (v_mfma_f32_32x32x16_bf16 / _f16), the packed dot product of the temporal attention and the bit pattern of 1.0 differ.
+// A single-storage source (fp32 or run-time dtype codes, no twin) is compiled once and uses none of the macros below.
 // A3D_FN(name) appends the storage suffix to an entry-point name: a3d_gemm_bf16 / a3d_gemm_f16.
+// A3D_FN_BARE(name) is for the boundary entry points whose bf16 name carries no suffix: a3d_im2col_in / a3d_im2col_in_f16.
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 #ifdef A3D_STORAGE_F16
 #define A3D_FN(base) base##_f16
+#define A3D_FN_BARE(base) base##_f16
 typedef _Float16 h16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x2_t __attribute__((ext_vector_type(2)));
 constexpr uint16_t ONE16 = 0x3C00;       // 1.0
@@ -36,6 +39,7 @@ A3D_DEV float lo16(uint32_t w) { return (float)__builtin_bit_cast(h16x2_t, w)[0]
 A3D_DEV float hi16(uint32_t w) { return (float)__builtin_bit_cast(h16x2_t, w)[1]; }
 #else
 #define A3D_FN(base) base##_bf16
+#define A3D_FN_BARE(base) base
 typedef __bf16 h16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 h16x2_t __attribute__((ext_vector_type(2)));
 constexpr uint16_t ONE16 = 0x3F80;       // 1.0
@@ -92,6 +96,13 @@ A3D_DEV u32x2_t lds_tr16_b64(const uint16_t* ptr) {
   return __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16_t*)ptr));
 }
 
+// sum over the 64 lanes of a wave, left in every lane
+A3D_DEV float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // compile-time unrolled loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
 template <int N, typename F, int... I>
 A3D_DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -130,6 +141,14 @@ static inline int a3d_once_per_device(uint64_t& done_mask, F&& fn) {
   const int rc = fn();
   if (rc == 0) done_mask |= (1ull << d);
   return rc;
+}
+
+// 1-D grid of the grid-stride elementwise kernels: one thread per item, capped at 8192 workgroups
+static inline unsigned grid_for(int64_t items, int block = 256) {
+  int64_t g = (items + block - 1) / block;
+  if (g > 8192) g = 8192;
+  if (g < 1) g = 1;
+  return (unsigned)g;
 }
 
 static inline int a3d_launch_status() {

@@ -26,7 +26,6 @@
 // Only fp32 entry points: compiled out of the fp16-storage pass of build.py so they are exported once.
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 namespace {
 
 constexpr int DG_C = 16;            // channels per scale
@@ -976,4 +975,3 @@ extern "C" int a3d_dg_backward_f32(a3d_stream_t stream, int T, int N, int B, con
   }
   return a3d_launch_status();
 }
-#endif  // A3D_STORAGE_F16

@@ -1,16 +1,9 @@
-// Memory-bound helpers of the denoise step (gfx950): GEGLU, SiLU, channel concat, timestep
-// sinusoid, input im2col / output unpack (layout folds), CFG + DDIM epilogue.
-// All use 16-byte accesses and grid-stride loops capped at 2048 workgroups.
+// Memory-bound helpers of the denoise step (gfx950) that read or write 16-bit storage: GEGLU, SiLU, channel concat, timestep
+// sinusoid, input im2col / output unpack (layout folds), row softmax.  The fp32 pieces of the step are in pipeline_f32.hip.
+// All use 16-byte accesses and grid-stride loops over a capped grid (grid_for).
 #include "common.h"
 
 namespace {
-
-inline unsigned grid_for(int64_t items, int block = 256) {
-  int64_t g = (items + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 
 __global__ void geglu_kernel(const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int64_t M, int64_t N8) {
   const int64_t total = M * N8;
@@ -134,26 +127,6 @@ __global__ void unpack_out_kernel(const uint16_t* X, T* Y, int V, int C, int F, 
   }
 }
 
-__global__ void cfg_ddim_kernel(const float* eps_pair, const float* x, const float* first, float* x_prev,
-                                int64_t n, int C, int F, int64_t HW, float guidance, float sa_t, float s1a_t,
-                                float sa_p, float s1a_p) {
-  const int64_t per = (int64_t)C * F * HW, total = n * per;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t hw = i % HW;
-    const int f = (int)((i / HW) % F);
-    const int64_t vc = i / (HW * F);     // v*C + c
-    if (f == 0) { x_prev[i] = first[vc * HW + hw]; continue; }
-    const float eu = eps_pair[i], et = eps_pair[total + i];
-    const float e = eu + guidance * (et - eu);
-    const float x0 = (x[i] - s1a_t * e) / sa_t;
-    x_prev[i] = sa_p * x0 + s1a_p * e;
-  }
-}
-
-}  // namespace
-
-namespace {
-
 // row softmax of fp32 logits [M, N] -> bf16 probabilities (one wave per row, three passes over the L2-resident row)
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* X, int64_t ldx, uint16_t* Y, int64_t ldy, int64_t M, int N) {
   const int lane = threadIdx.x & 63;
@@ -184,72 +157,34 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* X, int64
   }
 }
 
-// y[b, o, p] = scale * (sum_c w[o, c] x[b, c, p]) + bias[o] on planar fp32 images with a handful of channels (VAE post_quant_conv)
-__global__ void channel_mix_kernel(const float* X, const float* Wm, const float* bias, float* Y, int B, int Cin, int Cout, int64_t HW, float scale) {
-  const int64_t total = (int64_t)B * HW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = i / HW, px = i % HW;
-    float xin[8];
-    for (int c = 0; c < Cin; ++c) xin[c] = X[(b * Cin + c) * HW + px];
-    for (int o = 0; o < Cout; ++o) {
-      float acc = 0.f;
-      for (int c = 0; c < Cin; ++c) acc = fmaf(Wm[o * Cin + c], xin[c], acc);
-      Y[(b * Cout + o) * HW + px] = fmaf(scale, acc, bias ? bias[o] : 0.f);
-    }
-  }
-}
-
 }  // namespace
 
-#ifdef A3D_STORAGE_F16
-#define A3D_SOFTMAX_ROWS a3d_softmax_rows_f32_f16
-#define A3D_IM2COL_IN a3d_im2col_in_f16
-#define A3D_UNPACK_OUT a3d_unpack_out_f16
-#else
-#define A3D_SOFTMAX_ROWS a3d_softmax_rows_f32_bf16
-#define A3D_IM2COL_IN a3d_im2col_in
-#define A3D_UNPACK_OUT a3d_unpack_out
-#endif
-
-extern "C" int A3D_SOFTMAX_ROWS(a3d_stream_t stream, const float* X, int64_t ldx, void* Y, int64_t ldy, int64_t M, int64_t N) {
+extern "C" int A3D_FN(a3d_softmax_rows_f32)(a3d_stream_t stream, const float* X, int64_t ldx, void* Y, int64_t ldy, int64_t M, int64_t N) {
   if (!X || !Y || M <= 0 || N <= 0 || N % 4 != 0 || N > 0x7fffffffLL || ldx % 4 != 0 || ldy % 4 != 0) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) & 15u) || (reinterpret_cast<uintptr_t>(Y) & 7u)) return A3D_EINVAL;
+  if (!a3d_aligned(16, X) || !a3d_aligned(8, Y)) return A3D_EINVAL;
   const int64_t nblk = (M + 3) / 4;
   if (nblk > 0x7fffffffLL) return A3D_EINVAL;
   softmax_rows_kernel<<<dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream>>>(X, ldx, (uint16_t*)Y, ldy, M, (int)N);
   return a3d_launch_status();
 }
 
-#ifndef A3D_STORAGE_F16
-extern "C" int a3d_channel_mix_f32(a3d_stream_t stream, const float* X, const float* W, const float* bias, float* Y,
-                                   int B, int Cin, int Cout, int64_t HW, float scale) {
-  if (!X || !W || !Y || B <= 0 || Cin <= 0 || Cin > 8 || Cout <= 0 || Cout > 8 || HW <= 0) return A3D_EINVAL;
-  channel_mix_kernel<<<dim3(grid_for((int64_t)B * HW)), dim3(256), 0, (hipStream_t)stream>>>(X, W, bias, Y, B, Cin, Cout, HW, scale);
-  return a3d_launch_status();
-}
-#endif
-
-#ifndef A3D_STORAGE_F16
-extern "C" const char* a3d_version(void) { return "animate3d_hip gfx950 r6 (bf16 + fp16 storage)"; }
-#endif
-
 extern "C" int A3D_FN(a3d_geglu)(a3d_stream_t stream, const void* X, int64_t ldx, void* Y, int64_t ldy, int64_t M, int64_t N) {
   if (!X || !Y || M <= 0 || N <= 0 || N % 8 || ldx % 8 || ldy % 8) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Y)) return A3D_EINVAL;
   geglu_kernel<<<grid_for(M * (N / 8)), 256, 0, (hipStream_t)stream>>>((const uint16_t*)X, ldx, (uint16_t*)Y, ldy, M, N / 8);
   return a3d_launch_status();
 }
 
 extern "C" int A3D_FN(a3d_silu)(a3d_stream_t stream, const void* X, void* Y, int64_t n) {
   if (!X || !Y || n <= 0 || n % 8) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Y)) return A3D_EINVAL;
   silu_kernel<<<grid_for(n / 8), 256, 0, (hipStream_t)stream>>>((const uint16_t*)X, (uint16_t*)Y, n / 8);
   return a3d_launch_status();
 }
 
 extern "C" int A3D_FN(a3d_activation)(a3d_stream_t stream, const void* X, void* Y, int64_t n, int mode) {
   if (!X || !Y || n <= 0 || n % 8 != 0 || mode < 0 || mode > 2) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Y)) return A3D_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (mode == 0) silu_kernel<<<grid_for(n / 8), 256, 0, s>>>((const uint16_t*)X, (uint16_t*)Y, n / 8);
   else if (mode == 1) act_kernel<1><<<grid_for(n / 8), 256, 0, s>>>((const uint16_t*)X, (uint16_t*)Y, n / 8);
@@ -259,7 +194,7 @@ extern "C" int A3D_FN(a3d_activation)(a3d_stream_t stream, const void* X, void* 
 
 extern "C" int A3D_FN(a3d_concat)(a3d_stream_t stream, const void* A, int64_t Ca, const void* Bsrc, int64_t Cb, void* Y, int64_t M) {
   if (!A || !Bsrc || !Y || M <= 0 || Ca <= 0 || Cb <= 0 || Ca % 8 || Cb % 8) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bsrc) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, A, Bsrc, Y)) return A3D_EINVAL;
   concat_kernel<<<grid_for(M * ((Ca + Cb) / 8)), 256, 0, (hipStream_t)stream>>>((const uint16_t*)A, Ca / 8, (const uint16_t*)Bsrc, Cb / 8, (uint16_t*)Y, M);
   return a3d_launch_status();
 }
@@ -271,7 +206,7 @@ extern "C" int A3D_FN(a3d_timestep_embed)(a3d_stream_t stream, const float* t, v
   return a3d_launch_status();
 }
 
-extern "C" int A3D_IM2COL_IN(a3d_stream_t stream, const void* sample, int dtype, void* Y, int V, int C, int F, int H, int W) {
+extern "C" int A3D_FN_BARE(a3d_im2col_in)(a3d_stream_t stream, const void* sample, int dtype, void* Y, int V, int C, int F, int H, int W) {
   if (!sample || !Y || V <= 0 || C <= 0 || F <= 0 || H <= 0 || W <= 0 || 9 * C > 64) return A3D_EINVAL;
   const unsigned g = grid_for((int64_t)V * F * H * W);
   hipStream_t s = (hipStream_t)stream;
@@ -284,7 +219,7 @@ extern "C" int A3D_IM2COL_IN(a3d_stream_t stream, const void* sample, int dtype,
   return a3d_launch_status();
 }
 
-extern "C" int A3D_UNPACK_OUT(a3d_stream_t stream, const void* X, void* Y, int dtype, int V, int C, int F, int H, int W) {
+extern "C" int A3D_FN_BARE(a3d_unpack_out)(a3d_stream_t stream, const void* X, void* Y, int dtype, int V, int C, int F, int H, int W) {
   if (!X || !Y || V <= 0 || C <= 0 || F <= 0 || H <= 0 || W <= 0) return A3D_EINVAL;
   const unsigned g = grid_for((int64_t)V * C * F * H * W);
   hipStream_t s = (hipStream_t)stream;
@@ -297,15 +232,3 @@ extern "C" int A3D_UNPACK_OUT(a3d_stream_t stream, const void* X, void* Y, int d
   return a3d_launch_status();
 }
 
-#ifndef A3D_STORAGE_F16
-extern "C" int a3d_cfg_ddim_step_f32(a3d_stream_t stream, const float* eps_pair, const float* x, const float* first_frame,
-                                     float* x_prev, int64_t n, int C, int F, int64_t HW, float guidance,
-                                     float alpha_t, float alpha_prev) {
-  if (!eps_pair || !x || !first_frame || !x_prev || n <= 0 || C <= 0 || F <= 0 || HW <= 0) return A3D_EINVAL;
-  if (alpha_t <= 0.f || alpha_t > 1.f || alpha_prev <= 0.f || alpha_prev > 1.f) return A3D_EINVAL;
-  cfg_ddim_kernel<<<grid_for(n * C * F * HW), 256, 0, (hipStream_t)stream>>>(
-      eps_pair, x, first_frame, x_prev, n, C, F, HW, guidance, sqrtf(alpha_t), sqrtf(1.f - alpha_t), sqrtf(alpha_prev),
-      sqrtf(1.f - alpha_prev));
-  return a3d_launch_status();
-}
-#endif

@@ -9,7 +9,6 @@
 //                          is rounded to fp32 once
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 #include <math.h>
 
 namespace {
@@ -62,5 +61,3 @@ extern "C" int a3d_mesh_vertex_normals_f32(a3d_stream_t stream, int T, int Nv, i
   vertex_normals_kernel<<<blocks_for(total), 256, 0, (hipStream_t)stream>>>(total, Nv, C, pos, faces, order, starts, nrm);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

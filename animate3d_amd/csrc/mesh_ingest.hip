@@ -11,7 +11,6 @@
 //   rigid_kernel          load_ply's transform of N Gaussians (gaussian_4d.py:196-260): position, log-scale, orientation
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 #include <math.h>
 
 namespace {
@@ -175,5 +174,3 @@ extern "C" int a3d_gaussians_rigid_f32(a3d_stream_t stream, int N, const float* 
   rigid_kernel<<<blocks_for(N), 256, 0, (hipStream_t)stream>>>(N, xyz_in, scaling_in, rotation_in, f, xyz, scaling, rotation);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -535,7 +535,7 @@ inline int gn_nchunk(int64_t rows) { return (int)((rows + GN_ROWS_PER_BLOCK - 1)
 
 }  // namespace
 
-#ifndef A3D_STORAGE_F16
+#ifndef A3D_STORAGE_F16      // host-only queries, one copy: they stay here because they share gn_nchunk / gn_dispatch with the twin launch below
 extern "C" int64_t a3d_group_norm_ws_floats(int B, int64_t rows, int groups) {
   return (int64_t)B * gn_nchunk(rows) * groups * 2 + (int64_t)B * groups * 2;
 }
@@ -555,10 +555,10 @@ static int group_norm_launch(int mode, a3d_stream_t stream, const void* X, void*
                              float* ws, double* sums, const float* stats_in, int B, int64_t rows, int C, int groups, float eps, int silu,
                              const void* Xb = nullptr, int C1 = 0) {
   if (!X || B <= 0 || !gn_geometry_ok(rows, C, groups)) return A3D_EINVAL;
-  if (Xb && (C1 <= 0 || C1 >= C || C1 % 8 != 0 || (reinterpret_cast<uintptr_t>(Xb) & 15u))) return A3D_EINVAL;
+  if (Xb && (C1 <= 0 || C1 >= C || C1 % 8 != 0 || !a3d_aligned(16, Xb))) return A3D_EINVAL;
   if (mode != 1 && (!Y || !gamma || !beta)) return A3D_EINVAL;
   if ((mode != 2 && !ws) || (mode == 1 && !sums) || (mode == 2 && !stats_in)) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Y)) return A3D_EINVAL;
   if (B > 65535) return A3D_EINVAL;
   GNParams p{};
   p.X = (const uint16_t*)X; p.Y = (uint16_t*)Y; p.gamma = gamma; p.beta = beta;
@@ -614,9 +614,7 @@ extern "C" int A3D_FN(a3d_layer_norm)(a3d_stream_t stream, const void* X, void* 
                                    const void* pe1, int64_t pe1_div, int64_t pe1_mod,
                                    const void* pe2, int64_t pe2_div, int64_t pe2_mod) {
   if (!X || !Y1 || !gamma || !beta || M <= 0 || C <= 0 || C % 8 != 0 || C > 1536) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y1) | reinterpret_cast<uintptr_t>(Y2)) & 15u) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 15u) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(pe1) | reinterpret_cast<uintptr_t>(pe2)) & 15u) return A3D_EINVAL;      // (read 16 bytes at a time)
+  if (!a3d_aligned(16, X, Y1, Y2, gamma, beta, pe1, pe2)) return A3D_EINVAL;      // (all read or written 16 bytes at a time)
   if ((pe1 && (pe1_div <= 0 || pe1_mod <= 0)) || (pe2 && (pe2_div <= 0 || pe2_mod <= 0))) return A3D_EINVAL;
   LNParams p{};
   p.X = (const uint16_t*)X; p.Y1 = (uint16_t*)Y1; p.Y2 = (uint16_t*)Y2; p.gamma = gamma; p.beta = beta;

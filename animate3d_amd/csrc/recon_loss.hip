@@ -17,8 +17,6 @@
 // (float)byte / 255.0f by IEEE division and inside = alpha byte >= 128, the bits the fp32 tensors of data/simple_multi_image.py:205-215 hold.
 #include "loss_reduce.h"
 
-#ifndef A3D_STORAGE_F16
-
 namespace {
 
 constexpr int RL_RUN = 8;                          // pixels per thread
@@ -303,5 +301,3 @@ extern "C" int a3d_recon_loss_rgba8_bwd_f32(a3d_stream_t stream, int B, int H, i
                                             const float* grad_out, float* d_image, float* d_alpha) {
   return recon_backward(stream, B, H, W, image, alpha, GtRgba8{gt_rgba8}, index, bg, coef_rgb, coef_mask, grad_out, d_image, d_alpha);
 }
-
-#endif  // A3D_STORAGE_F16

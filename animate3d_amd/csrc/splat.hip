@@ -16,7 +16,6 @@
 // Only fp32 entry points: compiled out of the fp16-storage pass of build.py so they are exported once.
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 namespace {
 
 constexpr int GS_TILE = 16;
@@ -717,4 +716,3 @@ extern "C" int a3d_gs_sum_batch_f32(a3d_stream_t stream, const float* src, float
   sum_leading((hipStream_t)stream, src, dst, B, M);
   return a3d_launch_status();
 }
-#endif  // A3D_STORAGE_F16

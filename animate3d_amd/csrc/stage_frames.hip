@@ -11,8 +11,6 @@
 // No atomics, no workspace, no host synchronisation, one launch each; a result depends on its own inputs only.
 #include "common.h"
 
-#ifndef A3D_STORAGE_F16
-
 namespace {
 
 constexpr int SF_BLOCK = 256;
@@ -85,5 +83,3 @@ extern "C" int a3d_frames_pack_u8(a3d_stream_t stream, int B, int H, int W, cons
                                                                          reinterpret_cast<uint32_t*>(rgba8));
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -12,7 +12,6 @@
 // Four launches at most, whatever the number of tensors; 4-byte accesses, consecutive threads on consecutive elements.
 #include "f32_common.h"
 
-#ifndef A3D_STORAGE_F16
 #include <math.h>
 
 namespace {
@@ -120,5 +119,3 @@ extern "C" int a3d_stage_adam_f32(a3d_stream_t stream, const a3d_stage_adam_entr
   }
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -19,8 +19,6 @@
 // The upstream gradient is read through a device pointer; nothing but the inputs is needed.
 #include "loss_reduce.h"
 
-#ifndef A3D_STORAGE_F16
-
 namespace {
 
 constexpr int IR_RUN = 32;                         // pixels per thread
@@ -363,5 +361,3 @@ extern "C" int a3d_gaussian_reg_bwd_f32(a3d_stream_t stream, int B, int N, const
                                                                               d_scales, d_opacity);
   return a3d_launch_status();
 }
-
-#endif  // A3D_STORAGE_F16

@@ -1,15 +1,9 @@
-// Backward / optimiser kernels of the training path (reference train.py:576-601 runs these through torch autograd
-// and torch.optim.AdamW).  All HBM-bound elementwise / reduction work: 16-byte accesses, fp32 arithmetic, 16-bit storage (bf16 / fp16
-// build); the matrix products of the backward pass reuse the forward GEMM / conv kernels on transposed operands.
+// Backward kernels of the training path (reference train.py:576-601 runs these through torch autograd; the fp32
+// optimiser is in train_optim.hip).  All HBM-bound elementwise / reduction work: 16-byte accesses, fp32 arithmetic, 16-bit storage (bf16 /
+// fp16 build); the matrix products of the backward pass reuse the forward GEMM / conv kernels on transposed operands.
 #include "common.h"
 
 namespace {
-
-A3D_DEV float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ------------------------------------------------------------------ transpose (weights and activations of the wgrad GEMMs)
 // Y[c][r] = X[r][c], r < rows, c < cols; Y columns rows .. rows_pad-1 are zero (the wgrad contraction needs K % 64 == 0).
@@ -642,53 +636,13 @@ int launch_tab_dp(hipStream_t s, const TABParams& p, int C) {
   return p.frames <= 16 ? launch_tab<16, DP>(s, p, C) : launch_tab<32, DP>(s, p, C);
 }
 
-#ifndef A3D_STORAGE_F16
-// ------------------------------------------------------------------ optimiser (fp32 master parameters in one flat buffer)
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) { const float v = g[i]; s = fmaf(v, v, s); }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
-}
-// ctrl[0] = factor applied to every gradient (1 / loss_scale, times the clip coefficient), ctrl[1] = 1 when the step must be skipped
-// (non-finite gradients: GradScaler semantics of train.py:583-590), ctrl[2] = gradient norm after unscaling
-__global__ void clip_ctrl_kernel(const float* __restrict__ sq, float max_norm, float inv_loss_scale, float* __restrict__ ctrl) {
-  const float norm = sqrtf(sq[0]) * inv_loss_scale;
-  const bool finite = isfinite(norm);
-  float coef = 1.f;
-  if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));        // torch.nn.utils.clip_grad_norm_
-  ctrl[0] = finite ? inv_loss_scale * coef : 0.f;
-  ctrl[1] = finite ? 0.f : 1.f;
-  ctrl[2] = norm;
-}
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                     int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2,
-                                                     const float* __restrict__ ctrl) {
-  const float gs = ctrl ? ctrl[0] : 1.f;
-  if (ctrl && ctrl[1] != 0.f) return;                                       // skipped step: parameters and moments untouched
-  const float step = lr / bc1, rs = rsqrtf(bc2);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float gi = g[i] * gs;
-    float pi = p[i] * (1.f - lr * wd);                                      // decoupled weight decay (torch.optim.AdamW)
-    const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
-    const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
-    pi -= step * mi / (sqrtf(vi) * rs + eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-#endif
-
 }  // namespace
 
 extern "C" int A3D_FN(a3d_transpose)(a3d_stream_t stream, const void* X, int64_t ldx, void* Y, int64_t ldy, int64_t rows, int64_t cols, int64_t rows_pad) {
   if (!X || !Y || rows <= 0 || cols <= 0 || rows_pad < rows || ldx < cols || ldy < rows_pad) return A3D_EINVAL;
   const int64_t bx = (rows_pad + 63) / 64, by = (cols + 63) / 64;
   if (bx > 0x7fffffffLL || by > 65535) return A3D_EINVAL;
-  const bool wide = cols % 8 == 0 && rows_pad % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 &&
-                    ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15u) == 0;
+  const bool wide = cols % 8 == 0 && rows_pad % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && a3d_aligned(16, X, Y);
   if (wide) transpose16_kernel<<<dim3((unsigned)bx, (unsigned)by), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)X, ldx, (uint16_t*)Y, ldy, rows, cols, rows_pad);
   else transpose_kernel<<<dim3((unsigned)bx, (unsigned)by), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)X, ldx, (uint16_t*)Y, ldy, rows, cols, rows_pad);
   return a3d_launch_status();
@@ -698,7 +652,7 @@ extern "C" int A3D_FN(a3d_colsum)(a3d_stream_t stream, const void* X, int64_t ld
   if (!X || !out || rows <= 0 || cols <= 0 || ldx < cols) return A3D_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (!accumulate) { if (hipError_t e = hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), s); e != hipSuccess) return (int)e; }
-  if (cols % 320 == 0 && ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15u) == 0) {
+  if (cols % 320 == 0 && ldx % 8 == 0 && a3d_aligned(16, X)) {
     const uint16_t* x = (const uint16_t*)X;
     if (cols % 2560 == 0) return launch_colsum_rows<64>(s, x, ldx, rows, cols, out, alpha);
     if (cols % 1280 == 0) return launch_colsum_rows<32>(s, x, ldx, rows, cols, out, alpha);
@@ -735,7 +689,7 @@ extern "C" int A3D_FN(a3d_layer_norm_bwd)(a3d_stream_t stream, const void* X, co
     if (hipError_t e = hipMemsetAsync(dbeta, 0, (size_t)C * sizeof(float), s); e != hipSuccess) return (int)e;
   }
   LNBParams p{(const uint16_t*)X, (const uint16_t*)dY, gamma, (uint16_t*)dX, dgamma, dbeta, M, C, eps};
-  const bool al16 = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(dX) | reinterpret_cast<uintptr_t>(gamma)) & 15u) == 0;
+  const bool al16 = a3d_aligned(16, X, dY, dX, gamma);
   if (al16 && C == 320) return launch_ln_bwd_rows<8>(s, p);
   if (al16 && C == 640) return launch_ln_bwd_rows<16>(s, p);
   if (al16 && C == 1280) return launch_ln_bwd_rows<32>(s, p);
@@ -807,28 +761,3 @@ extern "C" int A3D_FN(a3d_temporal_attn_bwd)(a3d_stream_t stream, const void* Q,
     default: return A3D_EUNSUPPORTED;
   }
 }
-
-#ifndef A3D_STORAGE_F16
-extern "C" int a3d_sqnorm_f32(a3d_stream_t stream, const float* g, int64_t n, float* out, int accumulate) {
-  if (!g || !out || n <= 0) return A3D_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (!accumulate) { if (hipError_t e = hipMemsetAsync(out, 0, sizeof(float), s); e != hipSuccess) return (int)e; }
-  int64_t blocks = (n + 2047) / 2048; if (blocks > 2048) blocks = 2048;
-  sqnorm_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(g, n, out);
-  return a3d_launch_status();
-}
-
-extern "C" int a3d_clip_ctrl_f32(a3d_stream_t stream, const float* sqnorm, float max_norm, float inv_loss_scale, float* ctrl) {
-  if (!sqnorm || !ctrl) return A3D_EINVAL;
-  clip_ctrl_kernel<<<dim3(1), dim3(1), 0, (hipStream_t)stream>>>(sqnorm, max_norm, inv_loss_scale, ctrl);
-  return a3d_launch_status();
-}
-
-extern "C" int a3d_adamw_f32(a3d_stream_t stream, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                              float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* ctrl) {
-  if (!p || !g || !m || !v || n <= 0 || bias_corr1 <= 0.f || bias_corr2 <= 0.f) return A3D_EINVAL;
-  int64_t blocks = (n + 1023) / 1024; if (blocks > 4096) blocks = 4096;
-  adamw_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ctrl);
-  return a3d_launch_status();
-}
-#endif

@@ -6,13 +6,6 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t items, int block = 256) {
-  int64_t g = (items + block - 1) / block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
 // dX[v, c, f, y, x] = scale * sum_{ky, kx} dCol[pixel (v, f, y - ky + 1, x - kx + 1)][(ky*3 + kx)*C + c] over the taps whose output pixel
 // exists: the gather form of the col2im scatter (no atomics, fixed summation order).  One thread per output element, x fastest, so
 // neighbouring lanes read neighbouring dCol rows; the 9 taps of a row are shared by 9 neighbours through the L2.
@@ -74,13 +67,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const uint16_t* P
 
 }  // namespace
 
-#ifdef A3D_STORAGE_F16
-#define A3D_IM2COL_IN_BWD a3d_im2col_in_bwd_f16
-#else
-#define A3D_IM2COL_IN_BWD a3d_im2col_in_bwd
-#endif
-
-extern "C" int A3D_IM2COL_IN_BWD(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale) {
+extern "C" int A3D_FN_BARE(a3d_im2col_in_bwd)(a3d_stream_t stream, const void* dCol, float* dX, int V, int C, int F, int H, int W, float scale) {
   if (!dCol || !dX || V <= 0 || C <= 0 || F <= 0 || H <= 0 || W <= 0 || 9 * C > 64) return A3D_EINVAL;
   if (!a3d_aligned(2, dCol) || !a3d_aligned(4, dX)) return A3D_EINVAL;
   im2col_in_bwd_kernel<<<grid_for((int64_t)V * C * F * H * W), 256, 0, (hipStream_t)stream>>>((const uint16_t*)dCol, dX, V, C, F, H, W, scale);
@@ -91,7 +78,7 @@ extern "C" int A3D_FN(a3d_softmax_rows_bwd)(a3d_stream_t stream, const void* P, 
                                            int64_t M, int64_t N, float alpha) {
   if (!P || !dP || !dS || M <= 0 || N <= 0 || N % 4 != 0 || N > 0x7fffffffLL || ldp < N || lddp < N || ldds < N) return A3D_EINVAL;
   if (ldp % 4 != 0 || lddp % 4 != 0 || ldds % 4 != 0) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(P) & 7u) || (reinterpret_cast<uintptr_t>(dP) & 15u) || (reinterpret_cast<uintptr_t>(dS) & 7u)) return A3D_EINVAL;
+  if (!a3d_aligned(8, P, dS) || !a3d_aligned(16, dP)) return A3D_EINVAL;
   const int64_t nblk = (M + 3) / 4;
   if (nblk > 0x7fffffffLL) return A3D_EINVAL;
   softmax_rows_bwd_kernel<<<dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream>>>((const uint16_t*)P, ldp, dP, lddp, (uint16_t*)dS, ldds, M,

@@ -169,7 +169,7 @@ static void wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t* splits, int64_t
   *rows_per_split = rps;
 }
 
-#ifndef A3D_STORAGE_F16
+#ifndef A3D_STORAGE_F16      // host-only query, one copy: it stays here because it shares wgrad_plan with the twin launch below
 extern "C" int64_t a3d_wgrad_ws_floats(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   int64_t sp, rps;
@@ -182,7 +182,7 @@ extern "C" int A3D_FN(a3d_wgrad)(a3d_stream_t stream, const void* dY, int64_t ld
                                   float* ws, int64_t M, int64_t N, int64_t K, float alpha, int accumulate) {
   if (!dY || !X || !dW || !ws || M <= 0 || N <= 0 || K <= 0 || N % 8 != 0 || K % 8 != 0 || lddy % 8 != 0 || ldx % 8 != 0) return A3D_EINVAL;
   if (lddy < N || ldx < K || lddw < K || N > 0x7fffffffLL || K > 0x7fffffffLL) return A3D_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(dY) & 15u) || (reinterpret_cast<uintptr_t>(X) & 15u) || (reinterpret_cast<uintptr_t>(ws) & 15u)) return A3D_EINVAL;
+  if (!a3d_aligned(16, dY, X, ws)) return A3D_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int64_t tiles_k = (K + 127) / 128, tiles = ((N + 127) / 128) * tiles_k;
   int64_t splits, rps;

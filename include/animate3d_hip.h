@@ -740,8 +740,10 @@ int a3d_clip_preprocess(a3d_stream_t stream, const float* rgb, int n_src, int in
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
  * IEEE fp16 as the storage type (same signature, same semantics, same fp32 accumulation / statistics / softmax; the MFMA is
  * v_mfma_f32_32x32x16_f16): the dtype the reference's 4D-SDS caller runs the UNet in (animatemv_guidance.py:339-346 casts
- * the model and every input to fp16; BASELINE.json configs 4 and 5).  Built from the same sources with -DA3D_STORAGE_F16
- * (animate3d_amd/build.py).  a3d_im2col_in_f16 / a3d_unpack_out_f16: the CALLER tensor's dtype is still the `dtype` argument,
+ * the model and every input to fp16; BASELINE.json configs 4 and 5).  Built from the same sources with -DA3D_STORAGE_F16:
+ * animate3d_amd/build.py compiles a source twice unless its SINGLE_STORAGE tuple lists it, and the fp32-only entry points
+ * (the 4-D stage, the optimiser, a3d_channel_mix_f32, a3d_cfg_ddim_step_f32, a3d_version) live in the listed sources and
+ * have no twin.  a3d_im2col_in_f16 / a3d_unpack_out_f16: the CALLER tensor's dtype is still the `dtype` argument,
  * the activation side is fp16; a3d_im2col_in_bwd_f16 reads fp16 dCol rows and still writes fp32.
  * --------------------------------------------------------------------------------------------------------------------- */
 int a3d_gemm_f16(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
