@@ -170,6 +170,11 @@ _SIGNATURES = {
     "a3d_image_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "a3d_gaussian_reg_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
     "a3d_gaussian_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    # the SDS-side glue (csrc/sds_glue.hip): a twin source; the backward is fp32 on both sides and has no twin
+    "a3d_sds_pack_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    "a3d_sds_epilogue_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f64, c_f64,
+                                      c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "a3d_sds_epilogue_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f32, c_vp, c_vp]),
     # the optimiser step of the 4-D stage (csrc/stage_optim.hip): fp32 only, no storage twin; table is a host pointer to StageAdamEntry
     "a3d_stage_adam_f32": (c_int, [c_vp, c_vp, c_int, c_f64, c_f64, c_f64, c_int, c_vp]),
     # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins

@@ -457,8 +457,11 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
     ``height``, ``width``).  Either may be a ``cameras.CameraBatch`` instead: ``batch["cameras"]`` (``data_view_cameras``) replaces ``c2w`` /
     ``fovy`` / ``timestamps`` of the images, ``batch["random_camera"]`` may be one (``RandomCameraSampler.sample``); ``render`` then gets
     ``cameras=`` and ``None`` for the three tensors, and only then.
-    ``guidance``: ``comp_rgb [B, H, W, 3] -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound); a step with a
-    guidance callable is the reference's ``load_guidance: true``.  ``loss``: the lambdas under the reference's names (``lambda_rgb``,
+    ``guidance``: a ``guidance.AnimateMVGuidance``, or any object with ``takes_batch = True``, is called as the reference calls
+    ``self.guidance`` (animate3d.py:196): ``guidance(comp_rgb, batch.get("prompt_utils"), **batch["random_camera"], rgb_as_latents=False,
+    generator=generator)["loss_sds"]``, with this step's cameras, a dict or a ``CameraBatch``.  A plain callable is ``comp_rgb [B, H, W, 3]
+    -> loss_sds`` (how ``sds.sds_guidance_loss`` is bound) and sees nothing else.  A step with a guidance is the reference's
+    ``load_guidance: true``.``loss``: the lambdas under the reference's names (``lambda_rgb``,
     ``lambda_mask``, ``lambda_sds``, ``lambda_arap``, ``arap_sample_num``, for the mesh branch ``arap_K``, and the six regulariser weights
     ``lambda_tv_loss``, ``lambda_depth_tv_loss``, ``lambda_sparsity``, ``lambda_position``, ``lambda_opacity``, ``lambda_scales``); a
     non-zero ``lambda_normal_tv`` raises ``NotImplementedError`` (the reference's renderer never produces ``comp_normal``), a negative
@@ -533,7 +536,11 @@ def training_step(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict,
             out = render(field, gaussians, None, None, None, cam.height, cam.width, bg, cameras=cam, **common)
         else:
             out = render(field, gaussians, cam["c2w"], cam["fovy"], cam["timestamps"], cam["height"], cam["width"], bg, **common)
-        loss_sds = float(loss["lambda_sds"]) * guidance(out["comp_rgb"])
+        if getattr(guidance, "takes_batch", False):               # the guidance object: this step's cameras reach the UNet (animate3d.py:196)
+            loss_sds = guidance(out["comp_rgb"], batch.get("prompt_utils"), **cam, rgb_as_latents=False, generator=generator)["loss_sds"]
+        else:
+            loss_sds = guidance(out["comp_rgb"])
+        loss_sds = float(loss["lambda_sds"]) * loss_sds
         total = total + loss_sds
         terms["loss_sds"] = loss_sds.detach()
     if lambda_arap > 0.0:
@@ -611,7 +618,8 @@ def fit(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict, optimizer
     the reference's order (``forward`` sets the rates before it renders, animate3d.py:116; Lightning steps afterwards).  Each step, on a
     shallow copy of ``batch``:
 
-    1. with a ``sampler`` (``cameras.RandomCameraSampler``): ``sampler.update_step(s)`` and, when ``step_kwargs`` holds a ``guidance``,
+    1. ``guidance.update_step(0, s)`` where the guidance has that method (``guidance.AnimateMVGuidance``: its timestep range; where
+       threestudio updates its ``Updateable`` modules); with a ``sampler`` (``cameras.RandomCameraSampler``): ``sampler.update_step(s)`` and, when ``step_kwargs`` holds a ``guidance``,
        ``batch["random_camera"] = sampler.sample(generator, rng=rng)``;
     2. ``optimizer.update_learning_rate(s)`` where the optimiser has that method (``stage_optim.StageAdam``; any torch optimiser works
        without it);
@@ -632,6 +640,7 @@ def fit(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict, optimizer
             raise TypeError(f"fit: {name} is the loop's to pass")
     update_rates = getattr(optimizer, "update_learning_rate", None)
     skipped = getattr(optimizer, "skipped", None)
+    update_guidance = getattr(step_kwargs.get("guidance"), "update_step", None)
     logs: Dict[str, torch.Tensor] = {}
 
     def log(key, i, value):
@@ -642,6 +651,8 @@ def fit(field: HexPlaneDeformation, gaussians: Gaussians, batch: Dict, optimizer
     for i in range(steps):
         s = start_step + i
         step_batch = dict(batch)
+        if update_guidance is not None:
+            update_guidance(0, s)
         if sampler is not None:
             sampler.update_step(s)
             if step_kwargs.get("guidance") is not None:

@@ -675,6 +675,40 @@ int a3d_gaussian_reg_bwd_f32(a3d_stream_t stream, int B, int N, const float* mea
                              float coef_scales, float coef_opacity, const float* grad_out, float* d_means, float* d_scales,
                              float* d_opacity);
 
+/* The SDS-side glue of the 4D-SDS step (csrc/sds_glue.hip; contract in animate3d_amd/sds.py, sds_recon_loss_fused): everything of
+ * AnimateMVDiffusionGuidance.compute_mvdream_recon_loss (animatemv_guidance.py:415-503) but the UNet call.  b videos of n views of f >= 2
+ * frames, c channels, P = h w.  latents, latents_noisy, latents_recon, noise_pred and grad are [(b n f), c, P] fp32; noise is
+ * [b, n, f - 1, c, P] fp32; t [b] int64 and table [table_len] fp32 (alphas_cumprod) live on the device, a = table[t[b]] with t clamped into
+ * the table.  sample and eps are the UNet's [2 b n, c, f, P] in (text, uncond) halves and timestep its [2 b n], all of `dtype`: A3D_F32, or
+ * the storage type of the entry point (A3D_BF16 for _bf16, A3D_F16 for _f16; the other one: A3D_EINVAL).
+ *   a3d_sds_pack          one launch: latents_noisy = frame 0 ? latents : sqrt(a) latents + sqrt(1 - a) noise; sample = latents_noisy in the
+ *                         "(b n) c f P" layout, both halves; timestep = t[b] per (half, b, view)
+ *   a3d_sds_epilogue      eps_cfg = eps_text + guidance_scale (eps_text - eps_uncond); x0(e) = (latents_noisy - sqrt(1 - a) e) / sqrt(a);
+ *                         with r = recon_std_rescale != 0: factor[b] = (std x0(eps_text) + 1e-8) / (std x0(eps_cfg) + 1e-8), the unbiased
+ *                         standard deviations over b's n (f - 1) c P diffused elements, and recon = r (x0 factor) + (1 - r) x0, else
+ *                         recon = x0(eps_cfg); frame 0 of latents_recon is frame 0 of latents; out[0] = 0.5 sum (latents - recon)^2 /
+ *                         (b n f) * f / (f - 1).  noise_pred (eps_cfg of every frame) may be NULL.  Three launches with r != 0, two without
+ *                         (stats may then be NULL).  latents_recon and noise_pred are fp32 arithmetic that rounds where the torch ops
+ *                         round.  The statistics and the loss are formed in fp64 from latents, noise and eps (noise: the tensor
+ *                         a3d_sds_pack diffused with): the statistics per block of 2 048 elements in two passes (mean, then squared
+ *                         deviations), merged per b in block order by the pairwise update of Chan, Golub and LeVeque, never as a
+ *                         difference of sums; the loss's block sums through the fixed tree of csrc/loss_reduce.h in fp64, stored as
+ *                         fp32 pairs (hi, lo) and added by one block in fp64, so out[0] carries one rounding.  stats [b, ceil(n (f - 1)
+ *                         c P / 2048), 4] fp64 workspace, n_stats its length in doubles; partials [2, n_partials] fp32 workspace,
+ *                         n_partials = b ceil(n f c P / 2048); anything else: A3D_EINVAL
+ *   a3d_sds_epilogue_bwd_f32   grad = (latents - latents_recon) coef grad_out[0], exactly 0 in frame 0; grad_out is read on the device;
+ *                         the caller passes coef = f / ((f - 1) b n f).  One launch, fp32 on both sides: no twin
+ * No atomics, no host synchronisation; two calls are bitwise equal and b's rows do not depend on the rest of the batch.  A3D_EINVAL before
+ * any launch for: a NULL required pointer, a size < 1, f < 2, b n f c P >= 2^40, a pointer not aligned to its element. */
+int a3d_sds_pack_bf16(a3d_stream_t stream, int b, int n, int f, int c, int P, const float* latents, const float* noise, const int64_t* t,
+                      const float* table, int table_len, int dtype, float* latents_noisy, void* sample, void* timestep);
+int a3d_sds_epilogue_bf16(a3d_stream_t stream, int b, int n, int f, int c, int P, const void* eps, int dtype, const float* latents_noisy,
+                          const float* latents, const float* noise, const int64_t* t, const float* table, int table_len,
+                          double guidance_scale, double recon_std_rescale, double* stats, int64_t n_stats, float* latents_recon,
+                          float* noise_pred, float* partials, int64_t n_partials, float* out);
+int a3d_sds_epilogue_bwd_f32(a3d_stream_t stream, int b, int n, int f, int c, int P, const float* latents, const float* latents_recon,
+                             float coef, const float* grad_out, float* grad);
+
 /* The optimiser step of the 4-D stage (csrc/stage_optim.hip; contract in animate3d_amd/stage_optim.py, StageAdam), fp32.  Replaces
  * torch.optim.Adam(l, lr=0.0, eps=1e-15) of custom/threestudio-animate3d/geometry/gaussian_4d.py:391 and the step that Lightning's
  * GradScaler drops when a gradient holds an inf or a NaN.
@@ -743,7 +777,7 @@ int a3d_clip_preprocess(a3d_stream_t stream, const float* rgb, int n_src, int in
  * the model and every input to fp16; BASELINE.json configs 4 and 5).  Built from the same sources with -DA3D_STORAGE_F16:
  * animate3d_amd/build.py compiles a source twice unless its SINGLE_STORAGE tuple lists it, and the fp32-only entry points
  * (the 4-D stage, the optimiser, a3d_channel_mix_f32, a3d_cfg_ddim_step_f32, a3d_version) live in the listed sources and
- * have no twin.  a3d_im2col_in_f16 / a3d_unpack_out_f16: the CALLER tensor's dtype is still the `dtype` argument,
+ * have no twin; a3d_sds_epilogue_bwd_f32 lives in a twin source and is compiled into its bf16 build only.  a3d_im2col_in_f16 / a3d_unpack_out_f16: the CALLER tensor's dtype is still the `dtype` argument,
  * the activation side is fp16; a3d_im2col_in_bwd_f16 reads fp16 dCol rows and still writes fp32.
  * --------------------------------------------------------------------------------------------------------------------- */
 int a3d_gemm_f16(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
@@ -837,6 +871,12 @@ int a3d_zero_insert2x_f16(a3d_stream_t stream, const void* dY, void* Z, int B, i
 int a3d_upsample2x_bwd_f16(a3d_stream_t stream, const void* dU, void* dX, int B, int H, int W, int He, int We, int C);
 int a3d_wgrad_f16(a3d_stream_t stream, const void* dY, int64_t lddy, const void* X, int64_t ldx, float* dW, int64_t lddw,
                    float* ws, int64_t M, int64_t N, int64_t K, float alpha, int accumulate);
+int a3d_sds_pack_f16(a3d_stream_t stream, int b, int n, int f, int c, int P, const float* latents, const float* noise, const int64_t* t,
+                     const float* table, int table_len, int dtype, float* latents_noisy, void* sample, void* timestep);
+int a3d_sds_epilogue_f16(a3d_stream_t stream, int b, int n, int f, int c, int P, const void* eps, int dtype, const float* latents_noisy,
+                         const float* latents, const float* noise, const int64_t* t, const float* table, int table_len,
+                         double guidance_scale, double recon_std_rescale, double* stats, int64_t n_stats, float* latents_recon,
+                         float* noise_pred, float* partials, int64_t n_partials, float* out);
 
 #ifdef __cplusplus
 }
