@@ -7,14 +7,14 @@ from typing import Tuple
 
 import torch
 
-from .hip_ops import _check, _p, load_library
+from .hip_ops import _p, call, load_library
 
 
 def launch(name: str, device: torch.device, *args):
     """Call the C-ABI entry point ``name(stream, *args)`` with ``device`` current and on ``device``'s current stream: the tensors behind
     ``args`` were allocated there, whichever device the caller has current.  A non-zero return code raises."""
     with torch.cuda.device(device):
-        _check(getattr(load_library(), name)(torch.cuda.current_stream(device).cuda_stream, *args), name)
+        call(load_library(), name, torch.cuda.current_stream(device).cuda_stream, args)
 
 
 def launch_reduced(name: str, device: torch.device, sizes, operands, n_sums: int, blocks, n_out: int) -> torch.Tensor:

@@ -1,5 +1,8 @@
-"""ctypes binding of libanimate3d_hip.so (C-ABI in include/animate3d_hip.h) + the op set the
-UNet host code is written against.
+"""ctypes binding of libanimate3d_hip.so + the op set the UNet host code is written against.
+
+The C header include/animate3d_hip.h is the binding's only source: ``parse_header`` reads every entry point's signature, the two enums and
+the ``#define A3D_*`` integers from its text, ``load_library`` types the library from that, and the header's constants are this module's
+attributes under their own names.  Only the two structs are written out here (tests/test_header_binding.py holds them to the header).
 
 torch is used here only for device memory (``torch.empty``), the current HIP stream handle and
 pointer extraction; every arithmetic op goes through the C-ABI.  There is NO fallback: if the
@@ -9,18 +12,22 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanimate3d_hip.so")
+_PKG = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.path.join(_PKG, "lib", "libanimate3d_hip.so")
+_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "animate3d_hip.h")
 _lib = None
 
 c_i64, c_int, c_f32, c_f64, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
 
 class _RowMapC(ctypes.Structure):
+    """a3d_rowmap of include/animate3d_hip.h."""
     _fields_ = [("gdiv", c_i64), ("ga", c_i64), ("gb", c_i64), ("seg_len", c_i64), ("seg_stride", c_i64), ("ld", c_i64)]
 
 
@@ -29,8 +36,81 @@ class StageAdamEntry(ctypes.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("step", c_vp), ("n", c_i64), ("lr", c_f64)]
 
 
-STAGE_ADAM_MAX_TENSORS = 32                                   # A3D_STAGE_ADAM_MAX_TENSORS
-STAGE_ADAM_BEGIN, STAGE_ADAM_CHECK, STAGE_ADAM_UPDATE = 1, 2, 4
+# ---- the header as the binding's source
+class Header(NamedTuple):
+    functions: dict      # entry point -> (restype, argtypes), in the header's order
+    constants: dict      # enumerator or #define A3D_* -> int
+    structs: dict        # typedef struct -> [(field, ctypes type)]
+
+
+_SCALARS = {"int": c_int, "int64_t": c_i64, "float": c_f32, "double": c_f64, "a3d_stream_t": c_vp}
+_POINTEES = {"void", "char", "int", "unsigned int", "uint8_t", "int64_t", "float", "double"}
+
+
+def _c_type(text: str, structs, named: bool = True):
+    """(ctypes type, name) of ``[const] T [*] [name]``.  Every pointer is ``c_void_p``, which takes an address, ``ctypes.byref`` and a
+    ctypes array alike (``const char*``: ``c_char_p``).  A ``T`` outside the header's vocabulary raises: nothing is guessed."""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    name = words.pop() if named and words else None
+    base, stars = " ".join(w for w in words if w != "*"), words.count("*")
+    if name is None or name.isidentifier():
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base], name
+        if stars == 1 and (base in _POINTEES or base in structs):
+            return (ctypes.c_char_p if base == "char" else c_vp), name
+    raise RuntimeError(f"animate3d_hip.h: no ctypes type known for {' '.join(text.split())!r}")
+
+
+def parse_header(text: str) -> Header:
+    """What the binding needs of the header's text.  Whatever is left over that is not ``T a3d_name(parameters);`` raises."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {m[1]: int(m[2], 0) for m in re.finditer(r"^#define\s+(A3D_\w+)\s+(\S+)\s*$", text, flags=re.M)}
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    wrapped = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S)
+    text = wrapped[1] if wrapped else text
+
+    def take(pattern):
+        nonlocal text
+        found = re.findall(pattern, text, flags=re.S)
+        text = re.sub(pattern, "", text, flags=re.S)
+        return found
+
+    take(r"\btypedef\s+void\s*\*\s*a3d_stream_t\s*;")
+    for body in take(r"\benum\s*\{(.*?)\}\s*;"):
+        for item in body.split(","):
+            name, _, value = item.partition("=")
+            constants[name.strip()] = int(value, 0)
+    structs = {}
+    for struct, body in take(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;"):
+        fields = structs[struct] = []
+        for decl in filter(str.strip, body.split(";")):          # ``T a, b, c;`` declares three fields of T
+            first, *more = decl.split(",")
+            ctype, name = _c_type(first, structs)
+            fields += [(n.strip(), ctype) for n in (name, *more)]
+    functions = {}
+    for decl in filter(str.strip, text.split(";")):
+        m = re.fullmatch(r"\s*(.+?)\b(a3d_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        if not m:
+            raise RuntimeError(f"animate3d_hip.h: cannot read {' '.join(decl.split())!r} as a declaration")
+        params = [] if m[3].strip() == "void" else m[3].split(",")
+        functions[m[2]] = (_c_type(m[1], structs, named=False)[0], [_c_type(p, structs)[0] for p in params])
+    return Header(functions, constants, structs)
+
+
+def read_header(path: str) -> Header:
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise RuntimeError(f"{path}: the C header that types the library cannot be read ({e.strerror})") from e
+
+
+_HEADER = read_header(_HEADER_PATH)
+EXPORTED_SYMBOLS = tuple(_HEADER.functions)
+globals().update(_HEADER.constants)          # A3D_EINVAL, A3D_GEMM_RING, A3D_ATTN_PLAIN, A3D_BF16, ...: each under the header's name
+STAGE_ADAM_MAX_TENSORS, STAGE_ADAM_BEGIN, STAGE_ADAM_CHECK, STAGE_ADAM_UPDATE = (
+    A3D_STAGE_ADAM_MAX_TENSORS, A3D_STAGE_ADAM_BEGIN, A3D_STAGE_ADAM_CHECK, A3D_STAGE_ADAM_UPDATE)   # noqa: F821
+_DTYPE_CODE = {torch.float32: A3D_F32, torch.bfloat16: A3D_BF16, torch.float16: A3D_F16}          # noqa: F821
 
 
 @dataclass(frozen=True)
@@ -63,151 +143,20 @@ def rowmap_covers(m: RowMap, groups: int, step: int, length: int, rows: int, dev
     return bool(int(idx.min()) >= 0 and int(idx.max()) < rows and torch.unique(idx).numel() == rows)
 
 
-# symbol -> (restype, argtypes); mirrors include/animate3d_hip.h line by line
-_SIGNATURES = {
-    "a3d_version": (ctypes.c_char_p, []),
-    "a3d_gemm_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_int]),
-    "a3d_gemm_ws_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_int,
-                                 c_vp, c_i64, ctypes.POINTER(c_i64)]),
-    "a3d_gemm2_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int]),
-    "a3d_gemm_geglu_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int]),
-    "a3d_conv3x3_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "a3d_conv3x3_ws_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_vp, c_i64, ctypes.POINTER(c_i64)]),
-    "a3d_flash_attn_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC),
-                                    c_int, c_int, c_int, c_i64, c_i64, c_f32, c_f32, c_int]),
-    "a3d_flash_attn_counted_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC),
-                                            c_int, c_int, c_int, c_i64, c_i64, c_f32, c_f32, c_int, c_vp]),
-    "a3d_flash_attn2_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC),
-                                     ctypes.POINTER(_RowMapC), c_int, c_int, c_int, c_i64, c_i64, c_i64, c_f32, c_f32, c_f32, c_int]),
-    "a3d_temporal_attn_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_i64, c_int, c_int, c_f32]),
-    "a3d_temporal_attn_sharded_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_i64, c_int, c_int, c_f32,
-                                               c_int, c_int, c_int, c_i64]),
-    "a3d_group_norm_ws_floats": (c_i64, [c_int, c_i64, c_int]),
-    "a3d_group_norm_plan": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_int)]),
-    "a3d_group_norm_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_f32, c_int]),
-    "a3d_group_norm2_bf16": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_f32, c_int]),
-    "a3d_group_norm_sums_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int]),
-    "a3d_group_norm_apply_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int]),
-    "a3d_layer_norm_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_f32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64]),
-    "a3d_geglu_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
-    "a3d_silu_bf16": (c_int, [c_vp, c_vp, c_vp, c_i64]),
-    "a3d_activation_bf16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int]),
-    "a3d_concat_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
-    "a3d_timestep_embed_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int]),
-    "a3d_im2col_in": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int]),
-    "a3d_unpack_out": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "a3d_gemm_f32out_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_f32]),
-    "a3d_softmax_rows_f32_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
-    "a3d_softmax_rows_bwd_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32]),
-    "a3d_im2col_in_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f32]),
-    "a3d_channel_mix_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_f32]),
-    "a3d_cfg_ddim_step_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_f32, c_f32, c_f32]),
-    # training path (include/animate3d_hip.h, "Training path" section)
-    "a3d_flash_attn_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                        ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC),
-                                        ctypes.POINTER(_RowMapC), c_int, c_int, c_int, c_i64, c_i64, c_int, c_f32, c_f32, c_int]),
-    "a3d_flash_attn_lse_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC),
-                                        c_int, c_int, c_int, c_i64, c_i64, c_f32, c_f32, c_int, c_vp]),
-    "a3d_attn_delta_bf16": (c_int, [c_vp, c_vp, c_vp, ctypes.POINTER(_RowMapC), ctypes.POINTER(_RowMapC), c_vp, c_int, c_int, c_int, c_i64]),
-    "a3d_temporal_attn_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_int, c_int, c_f32]),
-    "a3d_layer_norm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_f32, c_int]),
-    "a3d_group_norm_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int]),
-    "a3d_geglu_bwd_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
-    "a3d_transpose_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64]),
-    "a3d_wgrad_ws_floats": (c_i64, [c_i64, c_i64, c_i64]),
-    "a3d_wgrad_bf16": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32, c_int]),
-    "a3d_colsum_bf16": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_f32, c_int]),
-    "a3d_axpby_bf16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32]),
-    "a3d_zero_insert2x_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int]),
-    "a3d_upsample2x_bwd_bf16": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "a3d_sqnorm_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int]),
-    "a3d_clip_ctrl_f32": (c_int, [c_vp, c_vp, c_f32, c_f32, c_vp]),
-    "a3d_adamw_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp]),
-    # Gaussian splat rasterizer (include/animate3d_hip.h, csrc/splat.hip): fp32 only, no storage twins
-    "a3d_gs_preprocess_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gs_duplicate_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gs_tile_ranges_f32": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64]),
-    "a3d_gs_render_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gs_render_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                      c_vp, c_vp, c_vp]),
-    "a3d_gs_preprocess_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gs_sum_batch_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64]),
-    # 4-D deformation field (csrc/deform4d.hip): fp32 only, no storage twins
-    "a3d_dg_cells_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
-    "a3d_dg_mean_partials": (c_i64, [c_int]),
-    "a3d_dg_forward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                   c_vp, c_vp, c_vp]),
-    "a3d_dg_backward_ws_floats": (c_i64, [c_int, c_int, c_vp]),
-    "a3d_dg_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    # ARAP rigidity loss and its k-NN graph (csrc/arap.hip): fp32 only, no storage twins
-    "a3d_knn_f32": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_f32, c_vp, c_vp]),
-    "a3d_arap_energy_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_arap_backward_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_mesh_sample_neighbours": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
-    # mesh ingest (csrc/mesh_ingest.hip): fp32 only, no storage twins; rot9 / quat4 are host pointers to doubles
-    "a3d_mesh_vertex_gaussians_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
-                                              c_int, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gaussians_rigid_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
-    # mesh export (csrc/mesh_export.hip): fp32 only, no storage twin
-    "a3d_mesh_vertex_normals_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    # camera batches of the 4-D stage (csrc/camera_batch.hip): fp32 only, no storage twins; ranges10 is a host pointer to doubles
-    "a3d_cameras_spherical_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_cameras_random_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_f64,
-                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_cameras_from_c2w_f32": (c_int, [c_vp, c_int, c_vp, c_vp, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp]),
-    # reconstruction loss of the 4-D stage (csrc/recon_loss.hip): fp32 only, no storage twins
-    "a3d_recon_loss_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
-    "a3d_recon_loss_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
-    "a3d_recon_loss_rgba8_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f64, c_f64, c_vp, c_i64, c_vp]),
-    "a3d_recon_loss_rgba8_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
-    # frames of the 4-D stage (csrc/stage_frames.hip): 8-bit RGBA in and out, no storage twins
-    "a3d_frames_unpack_u8": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_frames_pack_u8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
-    # regularisers of the 4-D stage's step (csrc/stage_reg.hip): fp32 only, no storage twins
-    "a3d_image_reg_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
-    "a3d_image_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
-    "a3d_gaussian_reg_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_f64, c_vp, c_i64, c_vp]),
-    "a3d_gaussian_reg_bwd_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
-    # the SDS-side glue (csrc/sds_glue.hip): a twin source; the backward is fp32 on both sides and has no twin
-    "a3d_sds_pack_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
-    "a3d_sds_epilogue_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f64, c_f64,
-                                      c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    "a3d_sds_epilogue_bwd_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f32, c_vp, c_vp]),
-    # the optimiser step of the 4-D stage (csrc/stage_optim.hip): fp32 only, no storage twin; table is a host pointer to StageAdamEntry
-    "a3d_stage_adam_f32": (c_int, [c_vp, c_vp, c_int, c_f64, c_f64, c_f64, c_int, c_vp]),
-    # CLIP image pre-processing of rendered frames (csrc/clip_preprocess.hip): one dtype code, no storage twins
-    "a3d_clip_preprocess_lds_limit": (c_i64, []),
-    "a3d_clip_preprocess": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int,
-                                    c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp]),
-}
-# fp16-storage twins (include/animate3d_hip.h, last section): same signatures
-_UNSUFFIXED_TWINS = ("a3d_im2col_in", "a3d_unpack_out", "a3d_im2col_in_bwd")      # boundary kernels: the bf16 build has no suffix
-for _name in list(_SIGNATURES):
-    if _name.endswith("_bf16"):
-        _SIGNATURES[_name[:-5] + "_f16"] = _SIGNATURES[_name]
-    elif _name in _UNSUFFIXED_TWINS:
-        _SIGNATURES[_name + "_f16"] = _SIGNATURES[_name]
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-
-_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-A3D_EUNSUPPORTED = -2          # include/animate3d_hip.h
-
-
 def lib_path() -> str:
     return _LIB_PATH
 
 
 def load_library():
-    """dlopen the in-tree library and type every entry point.  Raises if it is absent."""
+    """dlopen the in-tree library and type every entry point as include/animate3d_hip.h declares it.  Raises if either is absent."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -m animate3d_amd.build` (or __graft_entry__.build()). "
                                "There is no CPU fallback for the MI355X kernels.")
+        functions = read_header(_HEADER_PATH).functions
         lib = ctypes.CDLL(_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in functions.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -229,8 +178,19 @@ def group_norm_plan(rows: int, C: int, groups: int) -> dict:
 
 def _check(rc: int, what: str):
     if rc != 0:
-        kind = {-1: "A3D_EINVAL (shape/alignment precondition)", -2: "A3D_EUNSUPPORTED"}.get(rc, f"hipError {rc}")
+        kind = {A3D_EINVAL: "A3D_EINVAL (shape/alignment precondition)", A3D_EUNSUPPORTED: "A3D_EUNSUPPORTED"}.get(rc, f"hipError {rc}")  # noqa: F821
         raise RuntimeError(f"{what} failed: {kind}")
+
+
+def call(lib, name: str, stream, args, what: str = "", tolerate=()):
+    """The one way a launching entry point is called: ``name(stream, *args)`` of ``lib``, which is the loaded library or the ``_Entry`` of
+    an op set (``args`` comes as the caller's tuple: this runs thousands of times per forward).  A return code other than 0 and those of ``tolerate`` raises, naming the symbol that ran (an ``_Entry`` has resolved the
+    storage twin) and ``what``, the caller's shapes.  Returns the code."""
+    fn = getattr(lib, name)
+    rc = fn(stream, *args)
+    if rc != 0 and rc not in tolerate:
+        _check(rc, f"{fn.__name__} {what}" if what else fn.__name__)
+    return rc
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -254,18 +214,13 @@ def on_model_device(method):
 
 
 class _Entry:
-    """Entry points of one storage type: attribute ``a3d_gemm_bf16`` resolves to ``a3d_gemm_f16`` for an fp16 op set."""
+    """Entry points of one storage type as plain attributes: ``a3d_gemm_bf16`` is the library's ``a3d_gemm_f16`` for an fp16 op set, and
+    so is every name whose ``_f16`` twin the header declares (``a3d_im2col_in`` -> ``a3d_im2col_in_f16``)."""
 
     def __init__(self, lib, f16: bool):
-        self._lib, self._f16 = lib, f16
-
-    def __getattr__(self, name):
-        if self._f16:
-            if name.endswith("_bf16"):
-                name = name[:-5] + "_f16"
-            elif name in _UNSUFFIXED_TWINS:
-                name = name + "_f16"
-        return getattr(self._lib, name)
+        for name in EXPORTED_SYMBOLS:
+            twin = (name[:-5] if name.endswith("_bf16") else name) + "_f16"
+            setattr(self, name, getattr(lib, twin if f16 and twin in EXPORTED_SYMBOLS else name))
 
 
 class HipOps:
@@ -326,11 +281,34 @@ class HipOps:
         r = int(self.reserved_cus)
         if not 0 <= r <= 0xFF:
             raise ValueError(f"reserved_cus = {self.reserved_cus}: the flags word of a3d_gemm / a3d_conv3x3 carries 0..255 reserved compute units")
-        return r | (0x100 if tile128 else (0x200 if ring else 0))
+        return r | (A3D_GEMM_TILE128 if tile128 else (A3D_GEMM_RING if ring else 0))    # noqa: F821
 
     # ---- helpers
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _launch(self, name: str, *args, what: str = "", tolerate=()):
+        """``call`` on this op set's stream (``_stream()`` spelled out: a frame less per launch); ``name`` is the bf16 spelling, ``self.lib``
+        holds the storage twin under it."""
+        return call(self.lib, name, torch.cuda.current_stream(self.device).cuda_stream, args, what, tolerate)
+
+    def _split_k(self, name: str, key, args, what: str) -> bool:
+        """The split-K sequence of ``name`` (a3d_gemm_ws / a3d_conv3x3_ws): ask once per launch shape ``key`` how many workspace bytes a
+        split launch of exactly ``args`` needs, then run it on the stream's workspace.  False: the shape does not split, nothing ran."""
+        need = self._ws_plan.get(key)
+        if need is None:
+            q = c_i64(0)
+            self._launch(name, *args, None, 0, ctypes.byref(q), what="(query) " + what)
+            need = self._ws_plan[key] = int(q.value)
+        if need > 0:
+            self._launch(name, *args, _p(self._workspace(need)), need, None, what=what)
+        return need > 0
+
+    def _f32(self, *shape) -> torch.Tensor:
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def _gn_workspace(self, B: int, rows: int, groups: int) -> torch.Tensor:
+        return self._f32(int(self.lib.a3d_group_norm_ws_floats(B, rows, groups)))
 
     def _act(self, t: torch.Tensor, name: str):
         if t.dtype != self.act_dtype or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
@@ -365,21 +343,14 @@ class HipOps:
         if bias is not None:
             assert bias.dtype == torch.float32 and bias.numel() == N
         flags = self._gemm_flags(tile128, ring)
-        args = (self._stream(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(rowbias), rb_div,
+        args = (_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(rowbias), rb_div,
                 _p(residual), residual.stride(0) if residual is not None else 0, _p(y), y.stride(0), M, N, K, alpha, beta, flags)
+        what = f"M={M} N={N} K={K}"
         if self.split_k and self.split_k_gemm and not tile128 and M <= 32768 and K >= 1152:
             key = ("gemm", M, N, K, x.stride(0), w.stride(0), y.stride(0), rb_div if rowbias is not None else 0, flags)
-            need = self._ws_plan.get(key)
-            if need is None:
-                q = c_i64(0)
-                _check(self.lib.a3d_gemm_ws_bf16(*args, None, 0, ctypes.byref(q)), f"a3d_gemm_ws_bf16 (query) M={M} N={N} K={K}")
-                need = self._ws_plan[key] = int(q.value)
-            if need > 0:
-                ws = self._workspace(need)
-                _check(self.lib.a3d_gemm_ws_bf16(*args, _p(ws), need, None), f"a3d_gemm_ws_bf16 M={M} N={N} K={K}")
+            if self._split_k("a3d_gemm_ws_bf16", key, args, what):
                 return y
-        rc = self.lib.a3d_gemm_bf16(*args)
-        _check(rc, f"a3d_gemm_bf16 M={M} N={N} K={K}")
+        self._launch("a3d_gemm_bf16", *args, what=what)
         return y
 
     def gemm2(self, xa, xb, w, bias=None):
@@ -393,12 +364,9 @@ class HipOps:
         if K1 % 64 or K % 64 or N % 8:
             return None
         y = self.empty(M, N)
-        rc = self.lib.a3d_gemm2_bf16(self._stream(), _p(xa), xa.stride(0), _p(xb), xb.stride(0), K1, _p(w), w.stride(0), _p(bias), _p(y), y.stride(0),
-                                     M, N, K, self._gemm_flags(False))
-        if rc == A3D_EUNSUPPORTED:
-            return None
-        _check(rc, f"a3d_gemm2_bf16 M={M} N={N} K={K1}+{K - K1}")
-        return y
+        rc = self._launch("a3d_gemm2_bf16", _p(xa), xa.stride(0), _p(xb), xb.stride(0), K1, _p(w), w.stride(0), _p(bias), _p(y), y.stride(0),
+                          M, N, K, self._gemm_flags(False), what=f"M={M} N={N} K={K1}+{K - K1}", tolerate=(A3D_EUNSUPPORTED,))   # noqa: F821
+        return None if rc else y
 
     @staticmethod
     def interleave_geglu(w: torch.Tensor) -> torch.Tensor:
@@ -414,9 +382,8 @@ class HipOps:
         M, K = x.shape
         N2 = w_il.shape[0]
         y = self.empty(M, N2 // 2)
-        rc = self.lib.a3d_gemm_geglu_bf16(self._stream(), _p(x), x.stride(0), _p(w_il), w_il.stride(0), _p(bias_il), _p(y), y.stride(0), M, N2, K,
-                                          self._gemm_flags(tile128))
-        _check(rc, f"a3d_gemm_geglu_bf16 M={M} N2={N2} K={K}")
+        self._launch("a3d_gemm_geglu_bf16", _p(x), x.stride(0), _p(w_il), w_il.stride(0), _p(bias_il), _p(y), y.stride(0), M, N2, K,
+                     self._gemm_flags(tile128), what=f"M={M} N2={N2} K={K}")
         return y
 
     def conv3x3(self, x, B: int, H: int, W: int, w, bias, *, stride: int = 1, up2x: bool = False, rowbias=None, rb_div: int = 1, residual=None,
@@ -441,20 +408,13 @@ class HipOps:
         if rowbias is not None:
             assert rowbias.is_contiguous() and rowbias.shape[1] == Cout
         flags = self._gemm_flags(tile128)
-        args = (self._stream(), _p(x), _p(w), _p(bias), _p(rowbias), rb_div, _p(residual), _p(y), B, H, W, Cin, Cout, stride, up_code, flags)
+        args = (_p(x), _p(w), _p(bias), _p(rowbias), rb_div, _p(residual), _p(y), B, H, W, Cin, Cout, stride, up_code, flags)
+        what = f"B={B} H={H} W={W} Cin={Cin} Cout={Cout} stride={stride} up={up2x}"
         if self.split_k and not tile128 and B * Ho * Wo <= 32768:
             key = ("conv", B, H, W, Cin, Cout, stride, up_code, rb_div if rowbias is not None else 0, flags)
-            need = self._ws_plan.get(key)
-            if need is None:
-                q = c_i64(0)
-                _check(self.lib.a3d_conv3x3_ws_bf16(*args, None, 0, ctypes.byref(q)), f"a3d_conv3x3_ws_bf16 (query) B={B} H={H} W={W} Cin={Cin} Cout={Cout}")
-                need = self._ws_plan[key] = int(q.value)
-            if need > 0:
-                ws = self._workspace(need)
-                _check(self.lib.a3d_conv3x3_ws_bf16(*args, _p(ws), need, None), f"a3d_conv3x3_ws_bf16 B={B} H={H} W={W} Cin={Cin} Cout={Cout}")
+            if self._split_k("a3d_conv3x3_ws_bf16", key, args, what):
                 return y, Ho, Wo
-        rc = self.lib.a3d_conv3x3_bf16(*args)
-        _check(rc, f"a3d_conv3x3_bf16 B={B} H={H} W={W} Cin={Cin} Cout={Cout} stride={stride} up={up2x}")
+        self._launch("a3d_conv3x3_bf16", *args, what=what)
         return y, Ho, Wo
 
     # ---- attention
@@ -471,25 +431,19 @@ class HipOps:
         assert k.stride(0) == v.stride(0)
         o = out if out is not None else self.empty(q.shape[0], C)
         qm, km, om = qmap.c(q.stride(0)), kmap.c(k.stride(0)), qmap.c(o.stride(0))
-        flags = (1 if accumulate else 0) | (2 if causal else 0) | (4 if exact else 0) | (8 if plain else 0)
+        flags = ((A3D_ATTN_ACCUMULATE if accumulate else 0) | (A3D_ATTN_CAUSAL if causal else 0) | (A3D_ATTN_EXACT if exact else 0)
+                 | (A3D_ATTN_PLAIN if plain else 0))                                                                       # noqa: F821
+        name, last = "a3d_flash_attn_bf16", ()            # the _lse and _counted entry points take one more pointer
         if with_lse:
-            lse = torch.empty((groups, heads, q_len), dtype=torch.float32, device=self.device)
-            rc = self.lib.a3d_flash_attn_lse_bf16(self._stream(), _p(q), _p(k), _p(v), _p(o), ctypes.byref(qm), ctypes.byref(km), ctypes.byref(om),
-                                                  groups, heads, D, q_len, kv_len, float(D) ** -0.5, out_scale,
-                                                  flags, _p(lse))
-            _check(rc, f"a3d_flash_attn_lse_bf16 groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len}")
-            return o, lse
-        if self.attn_counters is not None:
+            lse = self._f32(groups, heads, q_len)
+            name, last = "a3d_flash_attn_lse_bf16", (_p(lse),)
+        elif self.attn_counters is not None:
             cnt = self.attn_counters
             assert cnt.dtype == torch.int32 and cnt.is_cuda and cnt.numel() >= 3 and cnt.is_contiguous()
-            rc = self.lib.a3d_flash_attn_counted_bf16(self._stream(), _p(q), _p(k), _p(v), _p(o), ctypes.byref(qm), ctypes.byref(km), ctypes.byref(om),
-                                                      groups, heads, D, q_len, kv_len, float(D) ** -0.5, out_scale, flags, _p(cnt))
-            _check(rc, f"a3d_flash_attn_counted_bf16 groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len}")
-            return o
-        rc = self.lib.a3d_flash_attn_bf16(self._stream(), _p(q), _p(k), _p(v), _p(o), ctypes.byref(qm), ctypes.byref(km), ctypes.byref(om),
-                                          groups, heads, D, q_len, kv_len, float(D) ** -0.5, out_scale, flags)
-        _check(rc, f"a3d_flash_attn_bf16 groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len}")
-        return o
+            name, last = "a3d_flash_attn_counted_bf16", (_p(cnt),)
+        self._launch(name, _p(q), _p(k), _p(v), _p(o), ctypes.byref(qm), ctypes.byref(km), ctypes.byref(om), groups, heads, D, q_len, kv_len,
+                     float(D) ** -0.5, out_scale, flags, *last, what=f"groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len}")
+        return (o, lse) if with_lse else o
 
     def flash_attn2(self, q, k, v, k2, v2, qmap: RowMap, kmap: RowMap, kmap2: RowMap, groups: int, heads: int, q_len: int, kv_len: int,
                     kv_len2: int, *, out_scale2: float = 1.0):
@@ -502,10 +456,9 @@ class HipOps:
         assert k.stride(0) == v.stride(0) and k2.stride(0) == v2.stride(0)
         o = self.empty(q.shape[0], q.shape[1])
         qm, km, km2, om = qmap.c(q.stride(0)), kmap.c(k.stride(0)), kmap2.c(k2.stride(0)), qmap.c(o.stride(0))
-        rc = self.lib.a3d_flash_attn2_bf16(self._stream(), _p(q), _p(k), _p(v), _p(k2), _p(v2), _p(o), ctypes.byref(qm), ctypes.byref(km),
-                                           ctypes.byref(km2), ctypes.byref(om), groups, heads, D, q_len, kv_len, kv_len2, float(D) ** -0.5,
-                                           1.0, out_scale2, 0)
-        _check(rc, f"a3d_flash_attn2_bf16 groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len} kv_len2={kv_len2}")
+        self._launch("a3d_flash_attn2_bf16", _p(q), _p(k), _p(v), _p(k2), _p(v2), _p(o), ctypes.byref(qm), ctypes.byref(km),
+                     ctypes.byref(km2), ctypes.byref(om), groups, heads, D, q_len, kv_len, kv_len2, float(D) ** -0.5, 1.0, out_scale2, 0,
+                     what=f"groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len} kv_len2={kv_len2}")
         return o
 
     def temporal_attn(self, q, k, v, videos: int, frames: int, L: int, heads: int, *, q_f0: int = 0, q_frames: Optional[int] = None,
@@ -518,16 +471,15 @@ class HipOps:
         assert k.stride(0) == v.stride(0)
         o = self._act(out, "tattn.out") if out is not None else self.empty(q.shape[0], C)
         assert o.shape == (q.shape[0], C)
+        what = f"videos={videos} frames={frames} L={L} D={D} q_f0={q_f0} q_frames={q_frames}"
         if q_frames is None or q_frames == frames:
             assert q.stride(0) == k.stride(0)
-            rc = self.lib.a3d_temporal_attn_bf16(self._stream(), _p(q), _p(k), _p(v), q.stride(0), _p(o), o.stride(0),
-                                                 videos, frames, L, heads, D, float(D) ** -0.5)
+            self._launch("a3d_temporal_attn_bf16", _p(q), _p(k), _p(v), q.stride(0), _p(o), o.stride(0), videos, frames, L, heads, D,
+                         float(D) ** -0.5, what=what)
         else:
             assert q.shape[0] == videos * q_frames * L and k.shape[0] == videos * frames * L
-            rc = self.lib.a3d_temporal_attn_sharded_bf16(self._stream(), _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(o), o.stride(0),
-                                                         videos, frames, L, heads, D, float(D) ** -0.5, q_f0, q_frames, q_frames,
-                                                         videos * q_frames * L)
-        _check(rc, f"a3d_temporal_attn_bf16 videos={videos} frames={frames} L={L} D={D} q_f0={q_f0} q_frames={q_frames}")
+            self._launch("a3d_temporal_attn_sharded_bf16", _p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(o), o.stride(0), videos, frames, L,
+                         heads, D, float(D) ** -0.5, q_f0, q_frames, q_frames, videos * q_frames * L, what=what)
         return o
 
     # ---- normalisation
@@ -536,9 +488,9 @@ class HipOps:
         assert x.is_contiguous() and x.shape[0] == B * rows
         C = x.shape[1]
         y = self.empty(x.shape[0], C)
-        ws = torch.empty(int(self.lib.a3d_group_norm_ws_floats(B, rows, groups)), dtype=torch.float32, device=self.device)
-        rc = self.lib.a3d_group_norm_bf16(self._stream(), _p(x), _p(y), _p(gamma), _p(beta), _p(ws), B, rows, C, groups, eps, 1 if silu else 0)
-        _check(rc, f"a3d_group_norm_bf16 B={B} rows={rows} C={C}")
+        ws = self._gn_workspace(B, rows, groups)
+        self._launch("a3d_group_norm_bf16", _p(x), _p(y), _p(gamma), _p(beta), _p(ws), B, rows, C, groups, eps, 1 if silu else 0,
+                     what=f"B={B} rows={rows} C={C}")
         return y
 
     def group_norm2(self, xa, xb, B: int, rows: int, gamma, beta, groups: int, eps: float, silu: bool):
@@ -547,19 +499,18 @@ class HipOps:
         assert xa.is_contiguous() and xb.is_contiguous() and xa.shape[0] == B * rows == xb.shape[0]
         Ca, Cb = xa.shape[1], xb.shape[1]
         y = self.empty(xa.shape[0], Ca + Cb)
-        ws = torch.empty(int(self.lib.a3d_group_norm_ws_floats(B, rows, groups)), dtype=torch.float32, device=self.device)
-        rc = self.lib.a3d_group_norm2_bf16(self._stream(), _p(xa), Ca, _p(xb), Cb, _p(y), _p(gamma), _p(beta), _p(ws), B, rows, groups, eps, 1 if silu else 0)
-        _check(rc, f"a3d_group_norm2_bf16 B={B} rows={rows} C={Ca}+{Cb}")
+        ws = self._gn_workspace(B, rows, groups)
+        self._launch("a3d_group_norm2_bf16", _p(xa), Ca, _p(xb), Cb, _p(y), _p(gamma), _p(beta), _p(ws), B, rows, groups, eps, 1 if silu else 0,
+                     what=f"B={B} rows={rows} C={Ca}+{Cb}")
         return y
 
     def group_norm_sums(self, x, B: int, rows: int, groups: int) -> torch.Tensor:
         """fp64 [B, groups, 2] = (sum, sum of squares) of this rank's rows (first half of a GroupNorm spread over ranks)."""
         x = self._act(x, "gn.x")
         assert x.is_contiguous() and x.shape[0] == B * rows
-        ws = torch.empty(int(self.lib.a3d_group_norm_ws_floats(B, rows, groups)), dtype=torch.float32, device=self.device)
+        ws = self._gn_workspace(B, rows, groups)
         sums = torch.empty((B, groups, 2), dtype=torch.float64, device=self.device)
-        _check(self.lib.a3d_group_norm_sums_bf16(self._stream(), _p(x), _p(ws), _p(sums), B, rows, x.shape[1], groups),
-               f"a3d_group_norm_sums_bf16 B={B} rows={rows} C={x.shape[1]}")
+        self._launch("a3d_group_norm_sums_bf16", _p(x), _p(ws), _p(sums), B, rows, x.shape[1], groups, what=f"B={B} rows={rows} C={x.shape[1]}")
         return sums
 
     def group_norm_apply(self, x, B: int, rows: int, gamma, beta, groups: int, stats: torch.Tensor, silu: bool):
@@ -568,8 +519,8 @@ class HipOps:
         assert x.is_contiguous() and x.shape[0] == B * rows
         assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape == (B, groups, 2)
         y = self.empty(x.shape[0], x.shape[1])
-        _check(self.lib.a3d_group_norm_apply_bf16(self._stream(), _p(x), _p(y), _p(gamma), _p(beta), _p(stats), B, rows, x.shape[1], groups,
-                                                  1 if silu else 0), f"a3d_group_norm_apply_bf16 B={B} rows={rows} C={x.shape[1]}")
+        self._launch("a3d_group_norm_apply_bf16", _p(x), _p(y), _p(gamma), _p(beta), _p(stats), B, rows, x.shape[1], groups, 1 if silu else 0,
+                     what=f"B={B} rows={rows} C={x.shape[1]}")
         return y
 
     def layer_norm(self, x, gamma, beta, eps: float, pe1=None, pe1_div: int = 1, pe2=None, pe2_div: int = 1, two: bool = False):
@@ -583,10 +534,9 @@ class HipOps:
             if pe is not None:
                 self._act(pe, "ln.pe")
                 assert pe.is_contiguous() and pe.shape[1] == C
-        rc = self.lib.a3d_layer_norm_bf16(self._stream(), _p(x), _p(y1), _p(y2), _p(gamma), _p(beta), M, C, eps,
-                                          _p(pe1), pe1_div, pe1.shape[0] if pe1 is not None else 1,
-                                          _p(pe2), pe2_div, pe2.shape[0] if pe2 is not None else 1)
-        _check(rc, f"a3d_layer_norm_bf16 M={M} C={C}")
+        self._launch("a3d_layer_norm_bf16", _p(x), _p(y1), _p(y2), _p(gamma), _p(beta), M, C, eps,
+                     _p(pe1), pe1_div, pe1.shape[0] if pe1 is not None else 1,
+                     _p(pe2), pe2_div, pe2.shape[0] if pe2 is not None else 1, what=f"M={M} C={C}")
         return (y1, y2) if two else y1
 
     # ---- elementwise / layout
@@ -594,14 +544,14 @@ class HipOps:
         x = self._act(x, "geglu.x")
         M, N2 = x.shape
         y = self.empty(M, N2 // 2)
-        _check(self.lib.a3d_geglu_bf16(self._stream(), _p(x), x.stride(0), _p(y), y.stride(0), M, N2 // 2), "a3d_geglu_bf16")
+        self._launch("a3d_geglu_bf16", _p(x), x.stride(0), _p(y), y.stride(0), M, N2 // 2)
         return y
 
     def silu(self, x):
         x = self._act(x, "silu.x")
         assert x.is_contiguous()
         y = torch.empty_like(x)
-        _check(self.lib.a3d_silu_bf16(self._stream(), _p(x), _p(y), x.numel()), "a3d_silu_bf16")
+        self._launch("a3d_silu_bf16", _p(x), _p(y), x.numel())
         return y
 
     def activation(self, x, kind: str):
@@ -609,20 +559,20 @@ class HipOps:
         x = self._act(x, "act.x")
         assert x.is_contiguous()
         y = torch.empty_like(x)
-        _check(self.lib.a3d_activation_bf16(self._stream(), _p(x), _p(y), x.numel(), {"silu": 0, "quick_gelu": 1, "gelu": 2}[kind]), f"a3d_activation {kind}")
+        self._launch("a3d_activation_bf16", _p(x), _p(y), x.numel(), {"silu": 0, "quick_gelu": 1, "gelu": 2}[kind], what=kind)
         return y
 
     def concat(self, a, b):
         a, b = self._act(a, "concat.a"), self._act(b, "concat.b")
         assert a.is_contiguous() and b.is_contiguous() and a.shape[0] == b.shape[0]
         y = self.empty(a.shape[0], a.shape[1] + b.shape[1])
-        _check(self.lib.a3d_concat_bf16(self._stream(), _p(a), a.shape[1], _p(b), b.shape[1], _p(y), a.shape[0]), "a3d_concat_bf16")
+        self._launch("a3d_concat_bf16", _p(a), a.shape[1], _p(b), b.shape[1], _p(y), a.shape[0])
         return y
 
     def timestep_embed(self, t: torch.Tensor, dim: int):
         assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 1
         y = self.empty(t.shape[0], dim)
-        _check(self.lib.a3d_timestep_embed_bf16(self._stream(), _p(t), _p(y), t.shape[0], dim), "a3d_timestep_embed_bf16")
+        self._launch("a3d_timestep_embed_bf16", _p(t), _p(y), t.shape[0], dim)
         return y
 
     def im2col_in(self, sample: torch.Tensor):
@@ -631,14 +581,14 @@ class HipOps:
         sample = sample.contiguous()
         V, C, F, H, W = sample.shape
         y = self.empty(V * F * H * W, 64)
-        _check(self.lib.a3d_im2col_in(self._stream(), _p(sample), _DTYPE_CODE[sample.dtype], _p(y), V, C, F, H, W), "a3d_im2col_in")
+        self._launch("a3d_im2col_in", _p(sample), _DTYPE_CODE[sample.dtype], _p(y), V, C, F, H, W)
         return y
 
     def unpack_out(self, x, V: int, C: int, F: int, H: int, W: int, dtype: torch.dtype):
         x = self._act(x, "unpack.x")
         assert x.is_contiguous() and x.shape == (V * F * H * W, C)
         y = torch.empty((V, C, F, H, W), dtype=dtype, device=self.device)
-        _check(self.lib.a3d_unpack_out(self._stream(), _p(x), _p(y), _DTYPE_CODE[dtype], V, C, F, H, W), "a3d_unpack_out")
+        self._launch("a3d_unpack_out", _p(x), _p(y), _DTYPE_CODE[dtype], V, C, F, H, W)
         return y
 
     def gemm_f32out(self, x, w, bias=None, alpha: float = 1.0):
@@ -648,8 +598,7 @@ class HipOps:
         N = w.shape[0]
         assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        _check(self.lib.a3d_gemm_f32out_bf16(self._stream(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(y), N, M, N, K, alpha),
-               f"a3d_gemm_f32out M={M} N={N} K={K}")
+        self._launch("a3d_gemm_f32out_bf16", _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(y), N, M, N, K, alpha, what=f"M={M} N={N} K={K}")
         return y
 
     def softmax_rows(self, x, out=None):
@@ -658,7 +607,7 @@ class HipOps:
         M, N = x.shape
         y = self._act(out, "softmax_rows.out") if out is not None else self.empty(M, N)
         assert y.shape == (M, N)
-        _check(self.lib.a3d_softmax_rows_f32_bf16(self._stream(), _p(x), N, _p(y), y.stride(0), M, N), f"a3d_softmax_rows_f32_bf16 M={M} N={N}")
+        self._launch("a3d_softmax_rows_f32_bf16", _p(x), N, _p(y), y.stride(0), M, N, what=f"M={M} N={N}")
         return y
 
     def channel_mix(self, x, w, bias, scale: float = 1.0):
@@ -669,7 +618,7 @@ class HipOps:
         w = w.to(device=x.device, dtype=torch.float32).contiguous()
         b = None if bias is None else bias.to(device=x.device, dtype=torch.float32).contiguous()
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        _check(self.lib.a3d_channel_mix_f32(self._stream(), _p(x), _p(w), _p(b), _p(y), B, Cin, Cout, H * W, scale), "a3d_channel_mix_f32")
+        self._launch("a3d_channel_mix_f32", _p(x), _p(w), _p(b), _p(y), B, Cin, Cout, H * W, scale)
         return y
 
     # ---- VAE encoder input gradient (4D-SDS: vae_grad.py)
@@ -677,8 +626,8 @@ class HipOps:
         """Adjoint of ``im2col_in``: dCol [(V F) H W, 64] (storage type) -> fp32 [V, C, F, H, W] = scale * col2im(dCol)."""
         dcol = self._act(dcol, "im2col_in_bwd.dcol")
         assert dcol.is_contiguous() and dcol.shape == (V * F * H * W, 64)
-        dx = torch.empty((V, C, F, H, W), dtype=torch.float32, device=self.device)
-        _check(self.lib.a3d_im2col_in_bwd(self._stream(), _p(dcol), _p(dx), V, C, F, H, W, scale), f"a3d_im2col_in_bwd V={V} C={C} F={F} H={H} W={W}")
+        dx = self._f32(V, C, F, H, W)
+        self._launch("a3d_im2col_in_bwd", _p(dcol), _p(dx), V, C, F, H, W, scale, what=f"V={V} C={C} F={F} H={H} W={W}")
         return dx
 
     def softmax_rows_bwd(self, p, dp, alpha: float = 1.0, out=None):
@@ -689,8 +638,7 @@ class HipOps:
         M, N = p.shape
         y = self._act(out, "softmax_rows_bwd.out") if out is not None else self.empty(M, N)
         assert y.shape == (M, N)
-        _check(self.lib.a3d_softmax_rows_bwd_bf16(self._stream(), _p(p), p.stride(0), _p(dp), dp.stride(0), _p(y), y.stride(0), M, N, alpha),
-               f"a3d_softmax_rows_bwd M={M} N={N}")
+        self._launch("a3d_softmax_rows_bwd_bf16", _p(p), p.stride(0), _p(dp), dp.stride(0), _p(y), y.stride(0), M, N, alpha, what=f"M={M} N={N}")
         return y
 
     # ---- training path: backward kernels (reference: torch autograd behind train.py:576-590) and the optimiser step
@@ -731,19 +679,19 @@ class HipOps:
         if lse is not None:
             assert o is not None and lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() == groups * heads * q_len
             o = self._act(o, "attn_bwd.o")
-            lse2, delta = lse, torch.empty(groups * heads * q_len, dtype=torch.float32, device=self.device)
+            lse2, delta = lse, self._f32(groups * heads * q_len)
             om = qmap.c(o.stride(0))
-            rc = self.lib.a3d_attn_delta_bf16(self._stream(), _p(do), _p(o), ctypes.byref(dom), ctypes.byref(om), _p(delta), groups, heads, D, q_len)
-            _check(rc, f"a3d_attn_delta_bf16 groups={groups} heads={heads} D={D} q_len={q_len}")
+            self._launch("a3d_attn_delta_bf16", _p(do), _p(o), ctypes.byref(dom), ctypes.byref(om), _p(delta), groups, heads, D, q_len,
+                         what=f"groups={groups} heads={heads} D={D} q_len={q_len}")
             flags |= 2
         else:
-            stats = torch.empty((2, groups * heads * q_len), dtype=torch.float32, device=self.device)
+            stats = self._f32(2, groups * heads * q_len)
             lse2, delta = stats[0], stats[1]
         def run(dq_, dk_, dv_, dkm_, share, fl):
-            rc = self.lib.a3d_flash_attn_bwd_bf16(self._stream(), _p(q), _p(k), _p(v), _p(do), _p(dq_), _p(dk_), _p(dv_), _p(lse2), _p(delta),
-                                                  ctypes.byref(qm), ctypes.byref(km), ctypes.byref(dom), ctypes.byref(dqm), ctypes.byref(dkm_),
-                                                  groups, heads, D, q_len, kv_len, share, float(D) ** -0.5, do_scale, fl)
-            _check(rc, f"a3d_flash_attn_bwd_bf16 groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len} q_per_kv={share}")
+            self._launch("a3d_flash_attn_bwd_bf16", _p(q), _p(k), _p(v), _p(do), _p(dq_), _p(dk_), _p(dv_), _p(lse2), _p(delta),
+                         ctypes.byref(qm), ctypes.byref(km), ctypes.byref(dom), ctypes.byref(dqm), ctypes.byref(dkm_),
+                         groups, heads, D, q_len, kv_len, share, float(D) ** -0.5, do_scale, fl,
+                         what=f"groups={groups} heads={heads} D={D} q_len={q_len} kv_len={kv_len} q_per_kv={share}")
 
         # Shared keys (first-frame branches: the q_per_kv = F query groups of a video read frame 0's K / V): the kernel sums their dK | dV
         # inside one workgroup per key tile, i.e. groups / q_per_kv x key tiles x heads workgroups — 16 .. 256 at the training shapes,
@@ -791,10 +739,9 @@ class HipOps:
         C = q.shape[1]
         assert q.stride(0) == k.stride(0) == v.stride(0)
         d = self.empty(q.shape[0], 3 * C)
-        rc = self.lib.a3d_temporal_attn_bwd_bf16(self._stream(), _p(q), _p(k), _p(v), q.stride(0), _p(do), do.stride(0),
-                                                 _p(d), d.data_ptr() + 2 * C, d.data_ptr() + 4 * C, 3 * C,
-                                                 videos, frames, L, heads, C // heads, float(C // heads) ** -0.5)
-        _check(rc, f"a3d_temporal_attn_bwd_bf16 videos={videos} frames={frames} L={L} C={C}")
+        self._launch("a3d_temporal_attn_bwd_bf16", _p(q), _p(k), _p(v), q.stride(0), _p(do), do.stride(0),
+                     _p(d), d.data_ptr() + 2 * C, d.data_ptr() + 4 * C, 3 * C,
+                     videos, frames, L, heads, C // heads, float(C // heads) ** -0.5, what=f"videos={videos} frames={frames} L={L} C={C}")
         return d
 
     def layer_norm_bwd(self, x, dy, gamma, eps: float, need_param: bool = True):
@@ -802,10 +749,9 @@ class HipOps:
         assert x.is_contiguous() and dy.is_contiguous() and x.shape == dy.shape
         M, C = x.shape
         dx = self.empty(M, C)
-        dg = torch.empty(C, dtype=torch.float32, device=self.device) if need_param else None
-        db = torch.empty(C, dtype=torch.float32, device=self.device) if need_param else None
-        _check(self.lib.a3d_layer_norm_bwd_bf16(self._stream(), _p(x), _p(dy), _p(gamma), _p(dx), _p(dg), _p(db), M, C, eps, 0),
-               f"a3d_layer_norm_bwd_bf16 M={M} C={C}")
+        dg = self._f32(C) if need_param else None
+        db = self._f32(C) if need_param else None
+        self._launch("a3d_layer_norm_bwd_bf16", _p(x), _p(dy), _p(gamma), _p(dx), _p(dg), _p(db), M, C, eps, 0, what=f"M={M} C={C}")
         return dx, dg, db
 
     def group_norm_stats(self, x, B: int, rows: int, groups: int, eps: float) -> torch.Tensor:
@@ -821,19 +767,18 @@ class HipOps:
         assert x.is_contiguous() and dy.is_contiguous() and x.shape == dy.shape and x.shape[0] == B * rows
         C = x.shape[1]
         dx = self.empty(x.shape[0], C)
-        ws = torch.empty(B * C * 2, dtype=torch.float32, device=self.device)
+        ws = self._f32(B * C * 2)
         dg = torch.zeros(C, dtype=torch.float32, device=self.device) if need_param else None
         db = torch.zeros(C, dtype=torch.float32, device=self.device) if need_param else None
-        _check(self.lib.a3d_group_norm_bwd_bf16(self._stream(), _p(x), _p(dy), _p(gamma), _p(beta), _p(stats), _p(dx), _p(ws), _p(dg), _p(db),
-                                                B, rows, C, groups, 1 if silu else 0), f"a3d_group_norm_bwd_bf16 B={B} rows={rows} C={C}")
+        self._launch("a3d_group_norm_bwd_bf16", _p(x), _p(dy), _p(gamma), _p(beta), _p(stats), _p(dx), _p(ws), _p(dg), _p(db),
+                     B, rows, C, groups, 1 if silu else 0, what=f"B={B} rows={rows} C={C}")
         return dx, dg, db
 
     def geglu_bwd(self, proj_il, dy):
         proj_il, dy = self._act(proj_il, "geglu_bwd.p"), self._act(dy, "geglu_bwd.dy")
         M, N2 = proj_il.shape
         dp = self.empty(M, N2)
-        _check(self.lib.a3d_geglu_bwd_bf16(self._stream(), _p(proj_il), proj_il.stride(0), _p(dy), dy.stride(0), _p(dp), N2, M, N2 // 2),
-               f"a3d_geglu_bwd_bf16 M={M} N={N2 // 2}")
+        self._launch("a3d_geglu_bwd_bf16", _p(proj_il), proj_il.stride(0), _p(dy), dy.stride(0), _p(dp), N2, M, N2 // 2, what=f"M={M} N={N2 // 2}")
         return dp
 
     def transpose(self, x, pad: int = 64):
@@ -842,7 +787,7 @@ class HipOps:
         rows, cols = x.shape
         rp = (rows + pad - 1) // pad * pad
         y = self.empty(cols, rp)
-        _check(self.lib.a3d_transpose_bf16(self._stream(), _p(x), x.stride(0), _p(y), rp, rows, cols, rp), f"a3d_transpose_bf16 {rows}x{cols}")
+        self._launch("a3d_transpose_bf16", _p(x), x.stride(0), _p(y), rp, rows, cols, rp, what=f"{rows}x{cols}")
         return y
 
     def wgrad(self, dy, x, alpha: float = 1.0):
@@ -850,23 +795,22 @@ class HipOps:
         dy, x = self._act(dy, "wgrad.dy"), self._act(x, "wgrad.x")
         assert dy.shape[0] == x.shape[0]
         M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
-        dw = torch.empty((N, K), dtype=torch.float32, device=self.device)
-        ws = torch.empty(int(self.raw_lib.a3d_wgrad_ws_floats(M, N, K)), dtype=torch.float32, device=self.device)
-        _check(self.lib.a3d_wgrad_bf16(self._stream(), _p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), K, _p(ws), M, N, K, alpha, 0),
-               f"a3d_wgrad_bf16 M={M} N={N} K={K}")
+        dw = self._f32(N, K)
+        ws = self._f32(int(self.lib.a3d_wgrad_ws_floats(M, N, K)))
+        self._launch("a3d_wgrad_bf16", _p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), K, _p(ws), M, N, K, alpha, 0, what=f"M={M} N={N} K={K}")
         return dw
 
     def colsum(self, x, alpha: float = 1.0):
         x = self._act(x, "colsum.x")
-        out = torch.empty(x.shape[1], dtype=torch.float32, device=self.device)
-        _check(self.lib.a3d_colsum_bf16(self._stream(), _p(x), x.stride(0), x.shape[0], x.shape[1], _p(out), alpha, 0), "a3d_colsum_bf16")
+        out = self._f32(x.shape[1])
+        self._launch("a3d_colsum_bf16", _p(x), x.stride(0), x.shape[0], x.shape[1], _p(out), alpha, 0)
         return out
 
     def axpby_(self, x, y, a: float = 1.0, b: float = 1.0):
         """y <- a x + b y (in place on ``y``)."""
         x, y = self._act(x, "axpby.x"), self._act(y, "axpby.y")
         assert x.is_contiguous() and y.is_contiguous() and x.shape == y.shape
-        _check(self.lib.a3d_axpby_bf16(self._stream(), _p(x), _p(y), x.numel(), a, b), "a3d_axpby_bf16")
+        self._launch("a3d_axpby_bf16", _p(x), _p(y), x.numel(), a, b)
         return y
 
     def scaled(self, x, a: float):
@@ -876,33 +820,32 @@ class HipOps:
         dy = self._act(dy, "zero_insert.dy")
         assert dy.is_contiguous() and dy.shape[0] == B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1)
         z = self.empty(B * H * W, dy.shape[1])
-        _check(self.lib.a3d_zero_insert2x_bf16(self._stream(), _p(dy), _p(z), B, H, W, dy.shape[1]), "a3d_zero_insert2x_bf16")
+        self._launch("a3d_zero_insert2x_bf16", _p(dy), _p(z), B, H, W, dy.shape[1])
         return z
 
     def upsample2x_bwd(self, du, B: int, H: int, W: int, He: int, We: int):
         du = self._act(du, "upsample_bwd.du")
         assert du.is_contiguous() and du.shape[0] == B * He * We
         dx = self.empty(B * H * W, du.shape[1])
-        _check(self.lib.a3d_upsample2x_bwd_bf16(self._stream(), _p(du), _p(dx), B, H, W, He, We, du.shape[1]), "a3d_upsample2x_bwd_bf16")
+        self._launch("a3d_upsample2x_bwd_bf16", _p(du), _p(dx), B, H, W, He, We, du.shape[1])
         return dx
 
     def sqnorm(self, g: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False):
         assert g.dtype == torch.float32 and g.is_contiguous()
-        out = out if out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
-        _check(self.raw_lib.a3d_sqnorm_f32(self._stream(), _p(g), g.numel(), _p(out), 1 if accumulate else 0), "a3d_sqnorm_f32")
+        out = out if out is not None else self._f32(1)
+        self._launch("a3d_sqnorm_f32", _p(g), g.numel(), _p(out), 1 if accumulate else 0)
         return out
 
     def clip_ctrl(self, sq: torch.Tensor, max_norm: float, inv_loss_scale: float = 1.0):
-        ctrl = torch.empty(3, dtype=torch.float32, device=self.device)
-        _check(self.raw_lib.a3d_clip_ctrl_f32(self._stream(), _p(sq), max_norm, inv_loss_scale, _p(ctrl)), "a3d_clip_ctrl_f32")
+        ctrl = self._f32(3)
+        self._launch("a3d_clip_ctrl_f32", _p(sq), max_norm, inv_loss_scale, _p(ctrl))
         return ctrl
 
     def adamw_(self, p, g, m, v, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, step: int = 1, ctrl=None):
         for t in (p, g, m, v):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
         b1, b2 = betas
-        _check(self.raw_lib.a3d_adamw_f32(self._stream(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, weight_decay,
-                                          1.0 - b1 ** step, 1.0 - b2 ** step, _p(ctrl)), "a3d_adamw_f32")
+        self._launch("a3d_adamw_f32", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, weight_decay, 1.0 - b1 ** step, 1.0 - b2 ** step, _p(ctrl))
         return p
 
     def cfg_ddim_step(self, eps_pair, x, first_frame, guidance: float, alpha_t: float, alpha_prev: float):
@@ -912,6 +855,5 @@ class HipOps:
         n, C, F, H, W = x.shape
         assert eps_pair.shape == (2 * n, C, F, H, W) and first_frame.numel() == n * C * H * W
         y = torch.empty_like(x)
-        _check(self.lib.a3d_cfg_ddim_step_f32(self._stream(), _p(eps_pair), _p(x), _p(first_frame), _p(y), n, C, F, H * W,
-                                              guidance, alpha_t, alpha_prev), "a3d_cfg_ddim_step_f32")
+        self._launch("a3d_cfg_ddim_step_f32", _p(eps_pair), _p(x), _p(first_frame), _p(y), n, C, F, H * W, guidance, alpha_t, alpha_prev)
         return y
