@@ -53,7 +53,7 @@ STORAGE_VARIANTS = (("", []), ("_f16", ["-DA3D_STORAGE_F16"]))
 # entry points, which hip_ops.load_library() and tests/test_cabi.py refuse.
 SINGLE_STORAGE = (
     "arap.hip", "camera_batch.hip", "clip_preprocess.hip", "deform4d.hip", "mesh_export.hip", "mesh_ingest.hip", "pipeline_f32.hip",
-    "recon_loss.hip", "splat.hip", "stage_frames.hip", "stage_optim.hip", "stage_reg.hip", "train_optim.hip",
+    "recon_loss.hip", "splat.hip", "stage_frames.hip", "stage_optim.hip", "stage_reg.hip", "train_optim.hip", "video_io.hip",
 )
 
 

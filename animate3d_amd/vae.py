@@ -277,11 +277,8 @@ class AutoencoderKLDecoder(_VAEHalf):
         self._packed = P
         return P
 
-    @torch.no_grad()
-    @on_model_device
-    def decode(self, z: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
-        """AutoencoderKL.decode(z).sample for z [B, 4, h, w] (any float dtype) -> fp32 image [B, 3, 8h, 8w];
-        ``scale`` multiplies z first (decode_latents passes 1 / scaling_factor)."""
+    def _decode_rows(self, z: torch.Tensor, scale: float):
+        """The decoder up to and including conv_out for z [B, 4, h, w]: (rows [B H W, 4] in the storage type with channel 3 = padding, H, W)."""
         ops, cfg = self.ops, self.config
         P = self._packed if self._packed is not None else self._pack()
         B, Cz, H, W = z.shape
@@ -297,8 +294,16 @@ class AutoencoderKLDecoder(_VAEHalf):
                 x, H, W = ops.conv3x3(x, B, H, W, blk.up[0], blk.up[1], up2x=True)
         x = ops.group_norm(x, B, H * W, P.norm_out[0], P.norm_out[1], cfg.norm_num_groups, 1e-6, True)
         x, _, _ = ops.conv3x3(x, B, H, W, P.conv_out[0], P.conv_out[1])
-        img = ops.unpack_out(x, B, 4, 1, H, W, torch.float32)        # [B, 4, 1, H, W]; channel 3 is the padding
-        return img[:, : cfg.out_channels, 0].contiguous()
+        return x, H, W
+
+    @torch.no_grad()
+    @on_model_device
+    def decode(self, z: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+        """AutoencoderKL.decode(z).sample for z [B, 4, h, w] (any float dtype) -> fp32 image [B, 3, 8h, 8w];
+        ``scale`` multiplies z first (decode_latents passes 1 / scaling_factor)."""
+        x, H, W = self._decode_rows(z, scale)
+        img = self.ops.unpack_out(x, z.shape[0], 4, 1, H, W, torch.float32)        # [B, 4, 1, H, W]; channel 3 is the padding
+        return img[:, : self.config.out_channels, 0].contiguous()
 
     @torch.no_grad()
     def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
@@ -307,6 +312,21 @@ class AutoencoderKLDecoder(_VAEHalf):
         z = latents.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w)
         image = self.decode(z, scale=1.0 / self.config.scaling_factor)
         return image[None, :].reshape((b, f, -1) + image.shape[2:]).permute(0, 2, 1, 3, 4).float()
+
+    @torch.no_grad()
+    @on_model_device
+    def decode_frames_u8(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None, strip: bool = False) -> torch.Tensor:
+        """``decode_latents`` and the reference's post-processing of its result (tensor2vid -> VaeImageProcessor.postprocess -> numpy_to_pil,
+        pipeline.py:237-255) in bytes: latents [b, 4, F, h, w] -> uint8 [b, F, 8h, 8w, 3], or with ``strip`` the side-by-side
+        [F, 8h, b 8w, 3] of ``export_to_gif_mv``.  conv_out's rows go straight into ``video.video_to_u8``: no ``unpack_out``, no fp32 video; the
+        bytes are those of ``video_to_u8(decode_latents(latents))``, whose fp32 values are these rows widened.  ``out``: see ``video_to_u8``."""
+        from .video import video_to_u8
+        if self.config.out_channels != 3:
+            raise ValueError(f"decode_frames_u8 writes RGB bytes, the decoder has {self.config.out_channels} output channels")
+        b, c, f, h, w = latents.shape
+        z = latents.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w)
+        rows, H, W = self._decode_rows(z, 1.0 / self.config.scaling_factor)
+        return video_to_u8(rows, (b, f, H, W), out=out, strip=strip)
 
 
 class AutoencoderKLEncoder(_VAEHalf):

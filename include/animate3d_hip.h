@@ -770,6 +770,24 @@ int a3d_clip_preprocess(a3d_stream_t stream, const float* rgb, int n_src, int in
                         int off_x, const int* coef_y, const int* bounds_y, int ksize_y, int off_y, int tile_rows, int max_rows,
                         const float* table, int dtype, void* pixel_values, void* patch_rows, int patch, int kp, uint8_t* u8);
 
+/* The byte ends of MV-VDM generation (csrc/video_io.hip; host side in animate3d_amd/video.py, used by animate3d_amd/pipeline.py).  Elementwise,
+ * one launch each, no workspace, no atomics; a result depends on its own input value only.  A3D_EINVAL before any launch: a NULL operand, an
+ * extent <= 0, more than 2^31 - 1 pixels, a pixel size or channel count other than 3 or 4, a dtype code outside the enum, a misaligned pointer
+ * or stride as stated per entry point.
+ *   a3d_images_in_u8   images [n, H, W, cin] bytes (cin 3 or 4, a fourth channel is ignored; 4-byte aligned) -> planar [n, 3, H, W] fp32 =
+ *                      (b / 255.0f - 0.5f) / 0.5f with IEEE division and subtraction as written: the bits of torch's uint8 / 255 and
+ *                      Normalize(0.5, 0.5) on the CPU (animatediff/pipelines/pipeline.py:548-554).  unit (or NULL) [n, H, W, 3] fp32 = b / 255.0f:
+ *                      the float image a3d_clip_preprocess reads, whose (uint8)(v * 255.0f) is b for all 256 bytes.  planar, unit: 16-byte aligned
+ *   a3d_video_to_u8    video: dtype A3D_BF16 / A3D_F16: the VAE decoder's conv_out rows [(n F) H W, 4] (channel 3 is padding; needs W % 4 == 0,
+ *                      video 16-byte aligned, dst and the three strides multiples of 4); dtype A3D_F32: a planar video [n, 3, F, H, W] (any W;
+ *                      4-byte aligned; any dst and strides).  Pixel (v, f, y, x) goes to dst + v s_view + f s_frame + y s_row + x pixel as
+ *                      `pixel` bytes r g b [255]; strides in bytes, >= 0, s_row >= W pixel.  Per value: widen to fp32, t = x / 2 + 0.5,
+ *                      clamp to [0, 1], t * 255.0f rounded to fp32, round half to even: (images * 255).round().astype("uint8") of
+ *                      VaeImageProcessor.postprocess's (x / 2 + 0.5).clamp(0, 1).  A NaN gives 0 (numpy's cast of a NaN is not defined) */
+int a3d_images_in_u8(a3d_stream_t stream, const uint8_t* images, int n, int H, int W, int cin, float* planar, float* unit);
+int a3d_video_to_u8(a3d_stream_t stream, const void* video, int dtype, int n, int F, int H, int W, uint8_t* dst, int64_t s_view,
+                    int64_t s_frame, int64_t s_row, int pixel);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * fp16-storage twins.  Every entry point above that reads or writes 16-bit activations / weights exists a second time with
  * IEEE fp16 as the storage type (same signature, same semantics, same fp32 accumulation / statistics / softmax; the MFMA is
