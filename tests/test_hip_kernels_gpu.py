@@ -5,6 +5,7 @@ Tolerances (bf16 storage, fp32 accumulate): the reference is computed in fp32 fr
 inputs, so the only differences are fp32 summation order, the bf16 rounding of P in P·V and the final
 bf16 rounding of the output (relative 2^-9 = 2.0e-3).  Bars: relative L2 error <= 4e-3 for GEMM-like
 ops and attention, max-abs error <= 2 bf16 ulps of the output scale for normalisation/elementwise ops.
+Per-element claims about the GEMM / conv family (exact inputs, a float64 bound on every element) are in tests/test_gemm_edges_gpu.py.
 """
 
 import pytest
