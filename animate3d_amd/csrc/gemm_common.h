@@ -187,10 +187,13 @@ template <int NB> A3D_DEV void read_frags(const char* stage, uint32_t xrd, uint3
 // layout — a lane holds 4 consecutive columns of one row per register quad, the per-column vectors are broadcast LDS reads —
 // and ROUNDED 16-bit values go through the transposition buffer: a quarter (GEGLU) / half of the fp32 staging traffic, whose
 // ds_write_b128 rate (~80 B/clk per CU) made the transposition the longest part of a K = 320 tile's epilogue.
-template <int EPI, int NB>
+// UPROW (the phase form of the up-sampling conv, gemm_pp.hip CONV 3): tile row m is source pixel (b, i, j) of an image Wd wide and is
+// stored to row (b, 2i + a, 2j + b') of the 2x larger output = 4 m - 2 (m mod Wd) + uprow, uprow = 2 a Wd + b'; only the row address changes.
+template <int EPI, int NB, bool UPROW = false>
 A3D_DEV void epilogue_rounded(const GemmParams& p, f32x16_t (&acc)[NB][2], float* const stg, const float* const bias_lds,
                               const uint16_t* const rowbias_lds, const int64_t m0, const int64_t n0, const int wm, const WaveCols<NB> wc,
-                              const int lane) {
+                              const int lane, const uint32_t uprow = 0) {
+  static_assert(!UPROW || EPI == EPI_LINEAR, "the up-sampling row map is a feature of the linear epilogue");
   const int wblk = wc.first, wblk_last = wc.last;
   auto pass_cols = [&](int ps) { return (2 * ps + 1 < NB) ? 64 : 32; };
   auto pass_col0 = [&](int ps) { return ((2 * ps + 1 < NB) ? wblk + 2 * ps : wblk_last) * 32; };
@@ -337,7 +340,11 @@ A3D_DEV void epilogue_rounded(const GemmParams& p, f32x16_t (&acc)[NB][2], float
       for (int j = 0; j < 4; ++j) {
         if (j * (64 / lpr) >= 32) continue;
         const int row = (64 / lpr) * j + lane / lpr;
-        const int64_t m = mbase + row;
+        int64_t m = mbase + row;
+        if constexpr (UPROW) {
+          const uint32_t ms = (uint32_t)m;                    // (conv inputs are below 4 GB: m < 2^25)
+          m = (int64_t)(4u * ms - 2u * (ms % (uint32_t)p.Wd) + uprow);
+        }
         const u32x4_t o = unswap(ob[j], row);
         *reinterpret_cast<u32x4_t*>(p.Y + m * p.ldy + nbase + 8 * cc) = o;
       }
@@ -432,8 +439,8 @@ A3D_DEV void epilogue_residual(const GemmParams& p, f32x16_t (&acc)[NB][2], floa
 }
 
 
-// gemm_pp.hip: the persistent 256 x (nb * 64) tile kernel (conv 0 | 1 | 2, epi EPI_*, nb 4 | 5); the caller (try_launch_persist,
-// gemm_conv.hip) has filled tiles_m / tiles_n (and ksplit / nk_item / ws for a split-K launch) and checked the shape
+// gemm_pp.hip: the persistent 256 x (nb * 64) tile kernel (conv 0 | 1 | 2 | 3, epi EPI_*, nb 4 | 5); the caller (try_launch_persist,
+// the folded up-sampling entry: gemm_conv.hip) has filled tiles_m / tiles_n (and ksplit / nk_item / ws for a split-K launch) and checked the shape
 __attribute__((visibility("hidden"))) int A3D_FN(a3d_launch_gemm_pp)(int conv, int epi, int nb, hipStream_t stream, const GemmParams& p, int cus);
 // gemm_ring.hip: the LDS-DMA ring kernel for small dense GEMMs (128 x (64 nb) tiles, nb = 2 | 4 | 5; EPI_LINEAR); the caller has checked the
 // shape and filled tiles_m / tiles_n

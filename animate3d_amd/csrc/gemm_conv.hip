@@ -643,6 +643,48 @@ extern "C" int A3D_FN(a3d_conv3x3_ws)(a3d_stream_t stream, const void* X, const 
   return conv_entry(stream, X, Wp, bias, rowbias, rb_div, R, Y, B, H, W, Cin, Cout, stride, up2x, flags, ws, ws_bytes, ws_needed);
 }
 
+// The nearest-2x up-sampling conv in its 2x2 phase form (gemm_pp.hip, CONV 3) over weights folded at pack time: Wf [4, Cout, 4 Cin], phase
+// p = 2a + b of output pixel (2i + a, 2j + b), a row = window position (r, c) then ci.  One persistent launch walks the four phases' tiles;
+// no other kernel serves it, so a shape the persistent kernel does not take is A3D_EINVAL (the caller keeps a3d_conv3x3 for those).
+// Tile width: the cost model of plan_persist without its fill rule and without split-K (the order of the K sum, hence the result, is the
+// same for both widths and for every grid size).
+extern "C" int A3D_FN(a3d_conv3x3_up2x_folded)(a3d_stream_t stream, const void* X, const void* Wf, const float* bias,
+                                            const void* rowbias, const void* R, void* Y,
+                                            int B, int H, int W, int Cin, int Cout, int flags) {
+  if (!X || !Wf || !Y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return A3D_EINVAL;
+  if (rowbias || R) return A3D_EINVAL;                                       // the up-samplers have neither
+  if (!gemm_flags_ok(flags) || a3d_gemm_kernel_of(flags) != 0) return A3D_EINVAL;
+  if (Cin % 64 != 0 || (Cout % 320 != 0 && Cout % 256 != 0)) return A3D_EINVAL;
+  const int64_t msrc = (int64_t)B * H * W;
+  if (msrc % PBM != 0) return A3D_EINVAL;
+  if (!a3d_aligned(16, X, Wf) || !a3d_aligned(16, bias) || !a3d_aligned(16, Y)) return A3D_EINVAL;
+  // 32-bit DMA offsets and 32-bit pixel arithmetic, as plan_persist asks of every conv
+  if (((uint64_t)msrc + 2u * (uint64_t)W + 2u) * (uint64_t)Cin * 2u >= (1ull << 32) || (uint64_t)Cin * 64u >= (1ull << 31)) return A3D_EINVAL;
+  const int cus_dev = device_cus();
+  if (cus_dev == 0) return A3D_EUNSUPPORTED;
+  const int reserved = a3d_gemm_reserved_cus_of(flags);
+  GemmParams p{};
+  p.X = (const uint16_t*)X; p.ldx = Cin; p.W = (const uint16_t*)Wf; p.ldw = (int64_t)4 * Cin;
+  p.bias = bias; p.rb_div = 1; p.Y = (uint16_t*)Y; p.ldy = Cout; p.ldr = Cout;
+  p.B = B; p.H = H; p.Wd = W; p.Cin = Cin; p.stride = 1; p.up = 1; p.He = 2 * H; p.We = 2 * W;
+  p.Ho = H; p.Wo = W;                                  // a tile row is a SOURCE pixel
+  p.M = 4 * msrc; p.N = Cout; p.K = (int64_t)4 * Cin;
+  p.alpha = 1.f; p.beta = 1.f; p.vec16 = 1;
+  p.ksplit = 1; p.nk_item = (int)(p.K / 64);
+  p.tiles_m = p.M / PBM;
+  int nb = 0;
+  int64_t best = -1;
+  for (int cand = 5; cand >= 4; --cand) {
+    if (Cout % (cand * 64) != 0) continue;
+    const int64_t tiles = p.tiles_m * (Cout / (cand * 64));
+    const int64_t rounds = (tiles + cus_dev - 1) / cus_dev;
+    const int64_t cost = rounds * (p.nk_item + 12) * cand * (cand == 4 ? 108 : 100);
+    if (best < 0 || cost < best) { best = cost; nb = cand; }
+  }
+  p.tiles_n = Cout / (nb * 64);
+  return A3D_FN(a3d_launch_gemm_pp)(3, EPI_LINEAR, nb, (hipStream_t)stream, p, cus_dev - reserved > 32 ? cus_dev - reserved : 32);
+}
+
 extern "C" int A3D_FN(a3d_gemm_geglu)(a3d_stream_t stream, const void* X, int64_t ldx, const void* W, int64_t ldw,
                                    const float* bias, void* Y, int64_t ldy, int64_t M, int64_t N2, int64_t K, int flags) {
   GemmParams p = dense_params(X, ldx, W, ldw, bias, nullptr, 1, nullptr, 0, Y, ldy, M, N2, K, 1.f, 0.f);

@@ -62,7 +62,12 @@ A3D_DEV void pp_tile_coords(int64_t t, int64_t tiles_m, int64_t tiles_n, int64_t
 
 // Four phases (k-steps of 16) per K-tile; the 4 + NB DMA pieces a wave issues per K-tile go three per phase into phases 0-2 (measured
 // against five-then-the-rest and against two k-steps per phase: profiles/r4_microbench_pp.log).
-// CONV: 0 = dense A, 1 = 3x3 conv gather (pad 1, stride 1|2), 2 = 3x3 conv over a nearest-2x upsampled input
+// CONV: 0 = dense A, 1 = 3x3 conv gather (pad 1, stride 1|2), 2 = 3x3 conv over a nearest-2x upsampled input,
+//       3 = the same conv in its 2x2 phase form over pack-time folded weights (a3d_conv3x3_up2x_folded): the nine taps of output pixel
+//       (2i + a, 2j + b) read only the 2x2 source window whose top-left pixel is (i - 1 + a, j - 1 + b), so each of the four phases
+//       p = 2a + b is a 2x2 convolution of the SOURCE image with its own weight matrix Wf[p] [N, 4 Cin] (16 MACs per output pixel, not 36).
+//       The tile list is phase-major: tile rows [p T, (p + 1) T) of the M = 4 B H W rows (T = B H W / 256) are phase p, the 256 rows of a
+//       tile are consecutive source pixels, addressed like CONV 1 with a 2x2 window; row m is stored to output pixel (b, 2i + a, 2j + b).
 // SPLIT: split-K work items (GemmParams::ksplit > 1) — a separate instantiation: the item bookkeeping and the fp32 partial stores cost the
 // unsplit kernels registers they do not have (the conv instantiations sit at 256)
 // TWO: two-source A operand (GemmParams::X2; dense only) — its own instantiation for the same reason
@@ -72,6 +77,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
   using PC = PPCfg<NB>;
   constexpr int PH = 1, NPH = 4;              // k-steps per phase, phases per K-tile
   constexpr int NP = 4 + NB;                  // DMA pieces per wave and K-tile: X 0..3, W 0..NB-1
+  constexpr int TW = CONV == 3 ? 2 : 3;       // conv window: TW x TW taps, NT mask bits per piece
+  constexpr int NT = TW * TW;
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   char* const smem_b = reinterpret_cast<char*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -108,6 +115,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
   const int64_t cbias = CONV ? ((int64_t)p.Wd + 1) * p.Cin : 0;
   int64_t ld_m0 = 0, ld_n0 = 0;
   int ld_par = 0;
+  int ld_ph = 0;                              // CONV 3: phase 2a + b of the tile being requested
   int ik0 = 0, itap = 0, ikx = 0, iky = 0;
   // 3x3 conv: byte address of (tap, channel slice) of the K-tile requested next relative to a lane's tap-(0,0) offset aoff[], advanced
   // incrementally with the K walk (round 5: recomputing it from (tap / 3, tap % 3, slice) in each of the three DMA phases of a K-tile
@@ -136,12 +144,17 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
     const int64_t kofs = SPLIT ? (CONV ? ((int64_t)(tt - tile_id * S) * nk / 9) * 64 : (int64_t)(tt - tile_id * S) * nk * 64) : 0;
     pp_tile_coords(tile_id, p.tiles_m, p.tiles_n, tile_m, tile_n);
     ld_m0 = tile_m * PBM; ld_n0 = tile_n * PC::BN;
+    if constexpr (CONV == 3) {                 // phase-major tile rows: ld_m0 becomes the tile's first SOURCE pixel
+      const uint32_t tsrc = (uint32_t)p.tiles_m >> 2;
+      ld_ph = (int)((uint32_t)tile_m / tsrc);
+      ld_m0 = (int64_t)((uint32_t)tile_m - (uint32_t)ld_ph * tsrc) * PBM;
+    }
     ik0 = 0; itap = 0; ikx = 0; iky = 0;
     ld_par ^= 1;
     if constexpr (CONV != 0) xck = (uint64_t)(uintptr_t)p.X - (uint64_t)cbias * 2u + (uint64_t)kofs * 2u;
     if constexpr (CONV == 0) xk = (uint64_t)(uintptr_t)(p.X + (ld_m0 + wid * 32) * p.ldx + kofs);
     if constexpr (TWO) xk2 = (uint64_t)(uintptr_t)(p.X2 + (ld_m0 + wid * 32) * p.ldx2);
-    wk = (uint64_t)(uintptr_t)(p.W + (ld_n0 + wid * (NB * 8)) * p.ldw + kofs);
+    wk = (uint64_t)(uintptr_t)(p.W + ((CONV == 3 ? (int64_t)ld_ph * p.N : 0) + ld_n0 + wid * (NB * 8)) * p.ldw + kofs);
     if (EPI == EPI_LINEAR && p.rowbias) rbk = (uint64_t)(uintptr_t)(p.rowbias + (ld_m0 / p.rb_div) * p.N + ld_n0);
     if constexpr (CONV != 0) {
       amask[0] = 0; amask[1] = 0;
@@ -166,19 +179,20 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
           }
           amask[i >> 1] |= (mask << (9 * (i & 1))) | ((uint32_t)(~oy & 1) << (18 + 2 * (i & 1))) | ((uint32_t)(~ox & 1) << (19 + 2 * (i & 1)));
         } else {
-          const int y0 = oy * p.stride - 1, x0 = ox * p.stride - 1;
+          // window top-left: tap (0, 0) of the conv, or (CONV 3, stride 1) source pixel (i - 1 + a, j - 1 + b) of the phase
+          const int y0 = oy * p.stride - 1 + (CONV == 3 ? ld_ph >> 1 : 0), x0 = ox * p.stride - 1 + (CONV == 3 ? ld_ph & 1 : 0);
           aoff[i] = (uint32_t)(((((int64_t)b * p.H + y0) * p.Wd + x0) * p.Cin + cbias) * 2 + slot * 16);
 #pragma unroll
-          for (int tp = 0; tp < 9; ++tp) {
-            const int yy = y0 + tp / 3, xx = x0 + tp % 3;
+          for (int tp = 0; tp < NT; ++tp) {
+            const int yy = y0 + tp / TW, xx = x0 + tp % TW;
             if (yy >= 0 && yy < p.H && xx >= 0 && xx < p.Wd) mask |= 1u << tp;
           }
-          amask[i >> 1] |= mask << (9 * (i & 1));
+          amask[i >> 1] |= mask << (NT * (i & 1));
         }
       }
       sok[0] = 0; sok[1] = 0;
 #pragma unroll
-      for (int bit = 0; bit < 18; ++bit) {
+      for (int bit = 0; bit < 2 * NT; ++bit) {
         if (__builtin_amdgcn_ballot_w64(((amask[0] >> bit) & 1u) != 0u) == ~0ull) sok[0] |= 1u << bit;
         if (__builtin_amdgcn_ballot_w64(((amask[1] >> bit) & 1u) != 0u) == ~0ull) sok[1] |= 1u << bit;
       }
@@ -213,7 +227,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
         const uint32_t mk = amask[i >> 1];
         uint32_t vo = aoff[i];
         if constexpr (CONV == 2) vo += (((mk >> (18 + 2 * (i & 1))) & 1u) ? yE : yO) + (((mk >> (19 + 2 * (i & 1))) & 1u) ? xE : xO);
-        const int bit = itap + 9 * (i & 1);
+        const int bit = itap + NT * (i & 1);
         if ((sok[i >> 1] >> bit) & 1u) {
           glds16_s(vo, (const void*)(uintptr_t)xck, d);          // whole piece inside the image: scalar base + per-lane 32-bit offset
         } else {
@@ -242,20 +256,20 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
     }
     if constexpr (B == NP) {
       if constexpr (CONV != 0) {
-        // K walk of the implicit GEMM: all nine taps of one 64-channel slice, then the next slice (W rows are [tap][Cin]: a tap is
+        // K walk of the implicit GEMM: all nine taps (CONV 3: the four window positions) of one 64-channel slice, then the next slice (W rows are [tap][Cin]: a tap is
         // Cin elements away).  Tap-major order touched a tile's whole input window (6 image rows x Cin) between two uses of the same
         // line — ~5 MB per XCD at level 0, more than its L2; this order re-reads a 32 KB slice nine times in a row.  gemm_kernel walks
         // the same order (conv_k0), so the two kernels stay bit-identical.
         const uint64_t cin2 = (uint64_t)(uint32_t)p.Cin * 2u;
         wk += cin2;
         ++itap;
-        if (++ikx == 3) { ikx = 0; ++iky; }
-        if (itap == 9) {                                  // next 64-channel slice, back to tap (0, 0)
-          itap = 0; iky = 0; wk -= 9u * cin2 - 128u;
-          if constexpr (CONV == 1) xck -= (2u * (uint64_t)(uint32_t)p.Wd + 2u) * cin2;
+        if (++ikx == TW) { ikx = 0; ++iky; }
+        if (itap == NT) {                                 // next 64-channel slice, back to tap (0, 0)
+          itap = 0; iky = 0; wk -= (uint64_t)NT * cin2 - 128u;
+          if constexpr (CONV != 2) xck -= ((uint64_t)(TW - 1) * (uint64_t)(uint32_t)p.Wd + (uint64_t)(TW - 1)) * cin2;
           xck += 128u;
-        } else if constexpr (CONV == 1) {
-          xck += ikx == 0 ? ((uint64_t)(uint32_t)p.Wd - 2u) * cin2 : cin2;
+        } else if constexpr (CONV != 2) {
+          xck += ikx == 0 ? ((uint64_t)(uint32_t)p.Wd - (uint64_t)(TW - 1)) * cin2 : cin2;
         }
       } else {
         if (TWO && ik0 >= (int)p.K1) xk2 += 128; else xk += 128;
@@ -307,7 +321,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
   for (;;) {
     int64_t tile_n, tile_m;
     pp_tile_coords(SPLIT ? (int64_t)((uint32_t)t / (uint32_t)S) : t, p.tiles_m, p.tiles_n, tile_m, tile_n);
-    const int64_t m0 = tile_m * PBM, n0 = tile_n * PC::BN;
+    int64_t m0 = tile_m * PBM;
+    const int64_t n0 = tile_n * PC::BN;
+    uint32_t uprow = 0;                       // CONV 3: m0 = the tile's first source pixel, uprow = 2 a Wd + b (epilogue_rounded's UPROW)
+    if constexpr (CONV == 3) {
+      const uint32_t tsrc = (uint32_t)p.tiles_m >> 2;
+      const uint32_t ph = (uint32_t)tile_m / tsrc;
+      m0 = (int64_t)((uint32_t)tile_m - ph * tsrc) * PBM;
+      uprow = (ph >> 1) * 2u * (uint32_t)p.Wd + (ph & 1u);
+    }
     const int64_t tnext = t + G;
 #pragma unroll
     for (int a = 0; a < NB; ++a)
@@ -362,7 +384,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const GemmParams p) {
       float* const stg = reinterpret_cast<float*>(smem_b + (buf ^ 1) * PC::STAGE) + wid * (32 * 68);
       const float* const bias_lds = bias_image(smem_b + PC::BIAS_OFF, cur_par);
       const uint16_t* const rowbias_lds = rowbias_image(smem_b + PC::BIAS_OFF, cur_par);
-      if constexpr (EPI == EPI_GEGLU || !RES) epilogue_rounded<EPI, NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
+      if constexpr (EPI == EPI_GEGLU || !RES) epilogue_rounded<EPI, NB, CONV == 3>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane, uprow);
       else epilogue_residual<NB>(p, acc, stg, bias_lds, rowbias_lds, m0, n0, wm, wc, lane);
     }
     if (tnext >= ntiles) break;
@@ -472,5 +494,10 @@ int launch_pp_conv(int epi, int nb, hipStream_t stream, const GemmParams& p, int
 int A3D_FN(a3d_launch_gemm_pp)(int conv, int epi, int nb, hipStream_t stream, const GemmParams& p, int cus) {
   if (conv == 0) return launch_pp_conv<0>(epi, nb, stream, p, cus);
   if (conv == 1) return launch_pp_conv<1>(epi, nb, stream, p, cus);
-  return launch_pp_conv<2>(epi, nb, stream, p, cus);
+  if (conv == 2) return launch_pp_conv<2>(epi, nb, stream, p, cus);
+  // the phase form of the up-sampling conv: bias only (no residual, no rowbias), never split
+  if (conv != 3 || epi != EPI_LINEAR || p.R || p.rowbias || p.ksplit > 1 || p.X2) return A3D_EUNSUPPORTED;
+  if (nb == 5) return launch_pp<3, EPI_LINEAR, 5, false>(stream, p, cus);
+  if (nb == 4) return launch_pp<3, EPI_LINEAR, 4, false>(stream, p, cus);
+  return A3D_EUNSUPPORTED;
 }

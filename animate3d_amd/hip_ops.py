@@ -143,6 +143,62 @@ def rowmap_covers(m: RowMap, groups: int, step: int, length: int, rows: int, dev
     return bool(int(idx.min()) >= 0 and int(idx.max()) < rows and torch.unique(idx).numel() == rows)
 
 
+# ---- the up-sampling conv's phase form (a3d_conv3x3_up2x_folded): pack-time weight folding and the shapes it serves
+# taps of one axis that read window position r of phase a: UP2X_TAPS[a][r]  (R_0(0) = {0}, R_0(1) = {1, 2}, R_1(0) = {0, 1}, R_1(1) = {2})
+UP2X_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def fold_up2x_sums(w: torch.Tensor) -> torch.Tensor:
+    """float64 [4, Cout, 4 Cin] tap sums of a packed 3x3 weight ``w`` [Cout, 9 Cin] (ky, kx, ci), on the host and UNROUNDED: phase
+    p = 2a + b of output pixel (2i + a, 2j + b), a row ordered window position (r, c) then ci (include/animate3d_hip.h)."""
+    Cout, K9 = w.shape
+    if K9 % 9:
+        raise ValueError(f"a packed 3x3 weight has 9 Cin columns, got {tuple(w.shape)}")
+    w64 = w.detach().to(device="cpu", dtype=torch.float64).view(Cout, 3, 3, K9 // 9)
+    wf = torch.zeros((4, Cout, 2, 2, K9 // 9), dtype=torch.float64)
+    for a in range(2):
+        for b in range(2):
+            for r in range(2):
+                for c in range(2):
+                    for ky in UP2X_TAPS[a][r]:
+                        for kx in UP2X_TAPS[b][c]:
+                            wf[2 * a + b, :, r, c] += w64[:, ky, kx]
+    return wf.view(4, Cout, 4 * (K9 // 9))
+
+
+def round_once(x64: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """float64 -> bf16 / fp16 with ONE round-to-nearest-even.  torch converts through float32, and two roundings to nearest can land one
+    ulp off the single one, so the float32 step rounds to odd instead (truncate, last bit = sticky): float32 keeps 13 bits more than either
+    16-bit type, which makes the second, nearest-even rounding exact."""
+    f = x64.to(torch.float32)
+    inexact = f.to(torch.float64) != x64
+    over = f.to(torch.float64).abs() > x64.abs()
+    f = torch.where(over, torch.nextafter(f, torch.zeros_like(f)), f)
+    bits = f.view(torch.int32) | inexact.to(torch.int32)
+    return bits.view(torch.float32).to(dtype)
+
+
+def fold_up2x_weights(w: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The folded weight [4, Cout, 4 Cin] of ``HipOps.conv3x3(..., folded=)`` for the packed 3x3 weight ``w`` [Cout, 9 Cin]: tap sums in
+    float64 on the host, rounded once to ``dtype`` (default: w's), on w's device.  A pack-time operation: never call it per forward."""
+    return round_once(fold_up2x_sums(w), dtype or w.dtype).to(w.device).contiguous()
+
+
+def up2x_folded_applies(B: int, H: int, W: int, Cin: int, Cout: int, *, up2x: bool, up_size=None, stride: int = 1, rowbias=None,
+                        residual=None, folded=None, tile128: bool = False, shape_independent: bool = False) -> bool:
+    """True when ``HipOps.conv3x3`` takes the phase-form entry point: folded weights are given, the output is the exact (2H, 2W) —
+    the cropped sizes' border groups would hold in-image taps — there is no row bias or residual, and the persistent kernel takes the
+    shape (a3d_conv3x3_up2x_folded's rules).  ``shape_independent``: the caller compares runs of different row counts bit for bit
+    (``HipOps.split_k`` off); whether a shape qualifies depends on its row count, so such runs keep the nine-tap kernel."""
+    if folded is None or not up2x or stride != 1 or rowbias is not None or residual is not None or tile128 or shape_independent:
+        return False
+    if up_size is not None and (int(up_size[0]), int(up_size[1])) != (2 * H, 2 * W):
+        return False
+    if (B * H * W) % 256 or Cin % 64 or (Cout % 320 and Cout % 256):
+        return False
+    return (B * H * W + 2 * W + 2) * Cin * 2 < 1 << 32
+
+
 def lib_path() -> str:
     return _LIB_PATH
 
@@ -230,6 +286,7 @@ class HipOps:
     fp32 accumulation, statistics and softmax; an fp16 model keeps 11 significant bits where bf16 keeps 8."""
 
     has_attn_lse = True      # flash_attn(with_lse=True) / flash_attn_bwd(o=..., lse=...): see autograd_ops._FlashAttn
+    has_up2x_folded = True   # conv3x3(..., folded=): the packs of unet.py / vae.py fold the up-sampling weights for op sets that say so
 
     def __init__(self, device: Optional[torch.device] = None, act_dtype: torch.dtype = torch.bfloat16, split_k: bool = True):
         """``split_k`` = False: only kernels whose results do not depend on the launch shape (bit-for-bit batch independence, a sharded forward
@@ -387,13 +444,24 @@ class HipOps:
         return y
 
     def conv3x3(self, x, B: int, H: int, W: int, w, bias, *, stride: int = 1, up2x: bool = False, rowbias=None, rb_div: int = 1, residual=None,
-                up_size=None, tile128: bool = False):
+                up_size=None, tile128: bool = False, folded=None):
         """x [B*H*W, Cin] -> (y [B*Ho*Wo, Cout], Ho, Wo); w packed [Cout, 9*Cin] (ky, kx, ci).  ``up_size`` = (Ho, Wo) forces
-        the size of the nearest upsampling in front of the conv (2H or 2H-1, likewise W: unet_motion_mv_model.py:831-837)."""
+        the size of the nearest upsampling in front of the conv (2H or 2H-1, likewise W: unet_motion_mv_model.py:831-837).
+        ``folded`` = ``fold_up2x_weights(w)`` [4, Cout, 4*Cin] (inference packs): the up-sampling conv runs in its 2x2 phase form, 16 MACs
+        per output pixel instead of 36, wherever ``up2x_folded_applies``; everywhere else this is the nine-tap kernel on ``w``."""
         x, w = self._act(x, "conv.x"), self._act(w, "conv.w")
         Cin = x.shape[1]
         Cout = w.shape[0]
         assert x.is_contiguous() and w.is_contiguous() and x.shape[0] == B * H * W and w.shape[1] == 9 * Cin
+        if up2x_folded_applies(B, H, W, Cin, Cout, up2x=up2x, up_size=up_size, stride=stride, rowbias=rowbias, residual=residual,
+                               folded=folded, tile128=tile128, shape_independent=not self.split_k):
+            assert folded.dtype == self.act_dtype and folded.is_cuda and folded.is_contiguous() and folded.shape == (4, Cout, 4 * Cin)
+            if bias is not None:
+                assert bias.dtype == torch.float32 and bias.numel() == Cout
+            y = self.empty(4 * B * H * W, Cout)
+            self._launch("a3d_conv3x3_up2x_folded_bf16", _p(x), _p(folded), _p(bias), None, None, _p(y), B, H, W, Cin, Cout,
+                         self._gemm_flags(False), what=f"B={B} H={H} W={W} Cin={Cin} Cout={Cout}")
+            return y, 2 * H, 2 * W
         He, We = (2 * H, 2 * W) if up2x else (H, W)
         up_code = 1 if up2x else 0
         if up_size is not None:

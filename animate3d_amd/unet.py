@@ -36,7 +36,7 @@ import torch.nn as nn
 from . import modules as M
 from .config import UNetConfig
 from .embeddings import sine_pos_2d, sinusoidal_pos_1d
-from .hip_ops import RowMap, on_model_device
+from .hip_ops import RowMap, fold_up2x_weights, on_model_device
 
 
 class UNet3DConditionOutput:
@@ -71,6 +71,7 @@ class MVUNetMotionModel(nn.Module):
         self._packed = None
         self._packed_frozen = None          # training: persistent pack of the frozen sub-modules (enable_training)
         self._pack_grad = False             # True while _pack_train re-packs trainable sub-modules under autograd
+        self._pack_fold = True              # False while _pack_train builds the frozen pack: only the inference forward reads up_folded
         self._train_ops = None              # AutogradOps over the op set once enable_training() was called
         self._active_ops = None
         self._cond = None                   # inference: the stacked conditioning projections of the running forward (_project_conditioning)
@@ -569,12 +570,17 @@ class MVUNetMotionModel(nn.Module):
         return out
 
     def _pack_block(self, blk: M.MotionBlock):
+        up = None if blk.upsamplers is None else (self._conv_w(blk.upsamplers[0].conv), self._f(blk.upsamplers[0].conv.bias))
+        # the up-sampling conv's phase form (a3d_conv3x3_up2x_folded) reads tap sums folded here, once per pack: float64 on the host,
+        # one rounding to the storage type.  Inference packs only — the differentiable path keeps the nine-tap kernel and its dgrad.
+        fold = up is not None and self._pack_fold and not self._pack_grad and getattr(self.ops, "has_up2x_folded", False)
         return SimpleNamespace(
+            up_folded=fold_up2x_weights(up[0]) if fold else None,
             resnets=[self._pack_resnet(r) for r in blk.resnets],
             t2d=[self._pack_t2d(t) for t in blk.attentions] if blk.has_cross_attention else None,
             motion=[self._pack_motion(m) for m in blk.motion_modules],
             down=None if blk.downsamplers is None else (self._conv_w(blk.downsamplers[0].conv), self._f(blk.downsamplers[0].conv.bias)),
-            up=None if blk.upsamplers is None else (self._conv_w(blk.upsamplers[0].conv), self._f(blk.upsamplers[0].conv.bias)))
+            up=up)
 
     def _pack(self):
         """Kernel-layout copies of the weights (bf16 [N, K] matrices, fp32 biases/affines), built once."""
@@ -1052,7 +1058,11 @@ class MVUNetMotionModel(nn.Module):
         # between steps (staged training: a module trained first and frozen later) must not leave its pre-training weights in the pack
         sig = tuple(p.requires_grad for p in self.parameters())
         if self._packed_frozen is None or sig != getattr(self, "_packed_frozen_sig", None):
-            self._packed_frozen = self._pack()
+            self._pack_fold = False
+            try:
+                self._packed_frozen = self._pack()
+            finally:
+                self._pack_fold = True
             self._packed_frozen_sig = sig
             self._packed = None                    # (_pack stored it as the inference pack; that one is rebuilt on demand)
             self._mark_persistent(self._packed_frozen)
@@ -1315,7 +1325,9 @@ class MVUNetMotionModel(nn.Module):
                 # the reference passes the next skip's size whenever a latent side is not a multiple of 2^(levels-1);
                 # when it is, that size is the plain 2x, so always naming it is the same arithmetic
                 lvl -= 1
-                x, h_, w_ = ops.conv3x3(x, B2, h_, w_, pk.up[0], pk.up[1], up2x=True, up_size=sizes[lvl])
+                # inference: the 2x2 phase form over the pack's folded weights where the shape qualifies (HipOps.conv3x3)
+                fold = {"folded": pk.up_folded} if self._active_ops is None and getattr(pk, "up_folded", None) is not None else {}
+                x, h_, w_ = ops.conv3x3(x, B2, h_, w_, pk.up[0], pk.up[1], up2x=True, up_size=sizes[lvl], **fold)
         x = ops.group_norm(x, B2, h_ * w_, P.norm_out[0], P.norm_out[1], cfg.norm_num_groups, cfg.norm_eps, True)
         x, _, _ = ops.conv3x3(x, B2, h_, w_, P.conv_out[0], P.conv_out[1])
         out_dtype = sample.dtype if sample.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32

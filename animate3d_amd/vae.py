@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from .autograd_ops import AutogradOps
 from .denoise import randn_like_reference
-from .hip_ops import on_model_device
+from .hip_ops import fold_up2x_weights, on_model_device
 
 
 @dataclass
@@ -272,6 +272,8 @@ class AutoencoderKLDecoder(_VAEHalf):
             v=(self._w(a.to_v.weight), self._f(a.to_v.bias)), o=(self._w(a.to_out[0].weight), self._f(a.to_out[0].bias)))
         P.up = [SimpleNamespace(res=[self._pack_resnet(r) for r in b.resnets],
                                 up=None if b.upsamplers is None else self._conv_w(b.upsamplers[0].conv)) for b in d.up_blocks]
+        for blk in P.up:        # the up-sampling convs' phase form reads tap sums folded once per pack (hip_ops.fold_up2x_weights)
+            blk.up_folded = fold_up2x_weights(blk.up[0]) if blk.up is not None and getattr(self.ops, "has_up2x_folded", False) else None
         P.norm_out = (self._f(d.conv_norm_out.weight), self._f(d.conv_norm_out.bias))
         P.conv_out = self._conv_w(d.conv_out, pad_out_to=4)
         self._packed = P
@@ -291,7 +293,8 @@ class AutoencoderKLDecoder(_VAEHalf):
             for r in blk.res:
                 x = self._resnet(x, B, H, W, r)
             if blk.up is not None:
-                x, H, W = ops.conv3x3(x, B, H, W, blk.up[0], blk.up[1], up2x=True)
+                fold = {"folded": blk.up_folded} if blk.up_folded is not None else {}
+                x, H, W = ops.conv3x3(x, B, H, W, blk.up[0], blk.up[1], up2x=True, **fold)
         x = ops.group_norm(x, B, H * W, P.norm_out[0], P.norm_out[1], cfg.norm_num_groups, 1e-6, True)
         x, _, _ = ops.conv3x3(x, B, H, W, P.conv_out[0], P.conv_out[1])
         return x, H, W

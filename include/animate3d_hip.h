@@ -138,6 +138,23 @@ int a3d_conv3x3_ws_bf16(a3d_stream_t stream, const void* X, const void* Wp, cons
                         int B, int H, int W, int Cin, int Cout, int stride, int up2x, int flags,
                         void* ws, int64_t ws_bytes, int64_t* ws_needed);
 
+/* The up-sampling convolution (a3d_conv3x3 with up2x = 1: exact 2H x 2W output, no crop) in its 2x2 PHASE FORM over weights folded at
+ * pack time.  The nine taps of output pixel (2i + a, 2j + b) read only the 2x2 window of source pixels whose top-left one is
+ * (i - 1 + a, j - 1 + b); taps that hit the same source pixel are summed once by the caller:
+ *   Wf[p = 2a + b][co][(r, c)][ci] = sum_{ky in R_a(r), kx in R_b(c)} Wp[co][ky][kx][ci],  R_0(0) = {0}, R_0(1) = {1, 2}, R_1(0) = {0, 1}, R_1(1) = {2}
+ *   Y[b, 2i + a, 2j + b', co] = bias[co] + sum_{r, c, ci} X[b, i - 1 + a + r, j - 1 + b' + c, ci] * Wf[p][co][(r, c)][ci]
+ * (source pixels outside the image read zero) — 16 MACs per output pixel instead of 36.  Wf is [4, Cout, 4 Cin], contiguous, summed in
+ * float64 and rounded ONCE to the storage type (animate3d_amd.hip_ops.fold_up2x_weights), so the result differs from a3d_conv3x3's by
+ * that one rounding of the weights; with weights whose tap sums are exact it is bit-identical.  X [B H W, Cin], Y [B 2H 2W, Cout].
+ * One launch of the persistent kernel walks all four phases; nothing else serves this entry point, so every shape that kernel does not
+ * take is A3D_EINVAL (keep a3d_conv3x3 for it): B H W % 256 != 0, Cin % 64 != 0, Cout a multiple of neither 320 nor 256, an input of
+ * 4 GB or more, pointers that are not 16-byte aligned.  It takes no row bias and no residual — the up-samplers have neither —: rowbias
+ * and R must be NULL (A3D_EINVAL otherwise).  bias may be NULL.  flags: A3D_GEMM_RESERVED_CUS only (a kernel choice is A3D_EINVAL).
+ * No split-K: the result does not depend on the grid. */
+int a3d_conv3x3_up2x_folded_bf16(a3d_stream_t stream, const void* X, const void* Wf, const float* bias,
+                                 const void* rowbias, const void* R, void* Y,
+                                 int B, int H, int W, int Cin, int Cout, int flags);
+
 /* softmax(Q K^T * scale) V per (group, head), flash-style (no score matrix in memory).
  *   O[row_o(g,s), h*D + d] = out_scale * attn(...)   (+ previous O contents if accumulate)
  * Replaces xformers.ops.memory_efficient_attention at attention_processor.py:103,233,268,
@@ -818,6 +835,9 @@ int a3d_conv3x3_ws_f16(a3d_stream_t stream, const void* X, const void* Wp, const
                        const void* rowbias, int64_t rb_div, const void* R, void* Y,
                        int B, int H, int W, int Cin, int Cout, int stride, int up2x, int flags,
                        void* ws, int64_t ws_bytes, int64_t* ws_needed);
+int a3d_conv3x3_up2x_folded_f16(a3d_stream_t stream, const void* X, const void* Wf, const float* bias,
+                                const void* rowbias, const void* R, void* Y,
+                                int B, int H, int W, int Cin, int Cout, int flags);
 int a3d_flash_attn_f16(a3d_stream_t stream, const void* Q, const void* K, const void* V, void* O,
                         const a3d_rowmap* qmap, const a3d_rowmap* kmap, const a3d_rowmap* omap,
                         int groups, int heads, int head_dim, int64_t q_len, int64_t kv_len,
